@@ -10,7 +10,10 @@ N GPUs (torchrun, one process per GPU): the box is decomposed 2x1x1 / 2x2x1 / 2x
 style blocks), every rank owns a 128^3 block (weak scaling: N=8 is BASELINE config 5, 256^3 = 16.8M
 cells), processor-patch halos and solver reductions go over RCCL (xGMI).
 
-Output: one JSON line (rank 0) with the driver's contract fields plus
+A plain run sets up, runs --warmup untimed and --steps timed steps, writes the last step's state if
+--dump-outputs DIR is given, and prints one JSON line (rank 0) with the driver's contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...). With --full the line also holds what
+further passes after the timed region measure, among them
   roofline      -- the dominant kernel's algorithmic bytes / its mean HIP-event duration,
   cpu_baseline  -- CPU-A: the OpenMP C++ implementation of the same step behind the same C ABI
                    (baseline/cpu_a), timed on this host's cores on the same 128^3 workload.
@@ -110,6 +113,7 @@ ROOF_KERNELS = SOLVER_KERNELS + ASSEMBLY_KERNELS + ("k_thermo_cells",)
 
 def parse():
     ap = argparse.ArgumentParser()
+    full = ap.add_argument_group("only with --full", "settings of the passes after the timed region; a plain run ignores them")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     # the chemistry's per-cell step sizes and the solvers' poll cadence settle over the first few steps (the first
@@ -122,8 +126,8 @@ def parse():
                     help="initial state: the reference's own 64^3 TGV 0/ fields tiled (BASELINE config 3), or the "
                          "analytic TGV")
     ap.add_argument("--dt", type=float, default=1e-6)
-    ap.add_argument("--kernel", default="auto",
-                    help="kernel of the primary roofline entry (auto: the HBM-bound kernel with the most time)")
+    full.add_argument("--kernel", default="auto",
+                      help="kernel of the primary roofline entry (auto: the HBM-bound kernel with the most time)")
     ap.add_argument("--chem", default="ode", choices=["ode", "dnn", "off"],
                     help="chemistry source: stiff ODE integration per cell (BASELINE config 3), the DF-ODENet "
                          "surrogate (MFMA fp16, config 4's path on the H2 nets) or off")
@@ -133,21 +137,32 @@ def parse():
                          "curve, plain Morton, or reverse Cuthill-McKee")
     ap.add_argument("--traversal", default="none", choices=["bricks", "strips4", "strips8", "strips16", "none"],
                     help="visiting order of the gather kernels over the blockMesh-ordered data (dfmi_set_traversal)")
-    ap.add_argument("--roof-steps", type=int, default=3, help="extra steps with per-kernel HIP events (rooflines)")
-    ap.add_argument("--cpu-n", type=int, default=128, help="cells per direction of the CPU-A baseline sample")
-    ap.add_argument("--cpu-steps", type=int, default=2, help="timed outer iterations of the CPU-A baseline")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-flame", action="store_true", help="skip the BASELINE config 2 (1D flame) side line")
+    full.add_argument("--roof-steps", type=int, default=3, help="extra steps with per-kernel HIP events (rooflines)")
+    full.add_argument("--cpu-n", type=int, default=128, help="cells per direction of the CPU-A baseline sample")
+    full.add_argument("--cpu-steps", type=int, default=2, help="timed outer iterations of the CPU-A baseline")
+    full.add_argument("--no-cpu", action="store_true")
+    full.add_argument("--no-flame", action="store_true", help="skip the BASELINE config 2 (1D flame) side line")
     ap.add_argument("--schemes", default="case", choices=["case", "gpu"],
                     help="convection schemes of div(phi,Yi_h) / div(phi,K) / div(hDiffCorrFlux): the case's own "
                          "(examples/dfLowMachFoam/notorch/threeD_reactingTGV/H2/cvodeIntegrator/system/fvSchemes: "
                          "limitedLinear01 / limitedLinear / cubic, what the reference CPU solver runs) or the "
                          "reference GPU path's hard-wired upwind / linear / linear; the other set is timed beside")
-    ap.add_argument("--alt-steps", type=int, default=5, help="timed steps with the other scheme set (0: skip)")
+    full.add_argument("--alt-steps", type=int, default=5, help="timed steps with the other scheme set (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the line reports: the roofline pass, the other "
+                         "scheme set (and halo setting), BASELINE configs 1, 2 and 4 and the CPU-A baseline. Without it "
+                         "the run sets up, warms up, times --steps steps and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write the state the last one left (T, p, rho, he, U, Y per cell, phi "
+                         "per face; rank 0's block; a fixed seeded sample of a large mesh) as DIR/<name>.npy, float64")
     ap.add_argument("--dry-run", action="store_true",
                     help="set up the ranks and their mesh blocks, print the line's layout fields, touch no GPU "
                          "(tests of the launcher and the decomposition on CPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    given = [a.option_strings[0] for a in full._group_actions if getattr(args, a.dest) != a.default]
+    if given and not args.full and not args.dry_run and os.environ.get("RANK", "0") == "0":
+        print(f"bench.py: {', '.join(given)} ignored without --full", file=sys.stderr)
+    return args
 
 
 def spawn_ranks(n_gpus: int) -> int:
@@ -531,6 +546,24 @@ def chem_step_stats(ctx, C):
             "wave_eff_tiles_4096": float(cost.mean() / tile) if tile else None}
 
 
+DUMP_SAMPLE = 1 << 18       # cells (and faces) written by --dump-outputs: 16-species fields stay under 64 MB
+
+
+def dump_outputs(ctx, m, S: int, path: str):
+    """--dump-outputs: what a host reads back after dfmi_time_step, as the last timed step left it. Meshes
+    with more than DUMP_SAMPLE cells are sampled: the same sorted, seeded cell and face indices every run."""
+    import numpy as np
+
+    def pick(n):
+        return slice(None) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    os.makedirs(path, exist_ok=True)
+    C, F = m.n_cells, m.n_faces
+    cells, faces = pick(C), pick(F)
+    for name, shape, idx in (("T", (C,), cells), ("p", (C,), cells), ("rho", (C,), cells), ("he", (C,), cells),
+                             ("U", (3, C), cells), ("Y", (S, C), cells), ("phi", (F,), faces)):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(ctx.get_field(name, shape)[..., idx]))
+
+
 def decomposition(world: int):
     """decomposePar blocks of the weak-scaling box: 2x1x1 / 2x2x1 / 2x2x2 (N = 8 is BASELINE config 5)"""
     return {1: (1, 1, 1), 2: (2, 1, 1), 4: (2, 2, 1), 8: (2, 2, 2)}.get(world, (world, 1, 1))
@@ -679,6 +712,35 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el, med = float(tt[0].item()), float(tt[1].item())
     stats = {e: ctx.solver_stats(e) for e in ("U", "Y", "E", "p")}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, m, table.S, args.dump_outputs)
+    cells_total = m.n_cells * world
+    value = cells_total * args.steps / el
+    head = {
+        "metric": "cell-updates/s (dfLowMachFoam outer iter)",
+        "value": value,
+        "unit": "cell-updates/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": el / args.steps * 1e3,
+        "ms_per_step_median": med,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "solver_iters": {e: s[0] for e, s in stats.items()},
+        "finite": bool(np.isfinite(ctx.get_field("T", (m.n_cells,))).all()),   # this rank's T after the timed steps
+    }
+    if not args.full:                              # the plain run: the headline alone
+        ctx.close()
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        if not head["finite"]:
+            sys.exit("bench.py: T is not finite after the timed steps")
+        return
 
     # ---- roofline pass: the same step, HIP events around every launch of the measured kernels and the
     # solver work counted on the device (after the headline, so the instrumentation never inflates it)
@@ -756,8 +818,6 @@ def main():
     opt_face_hex = ctx.get_option("fv.hex_walk") != 0 and ctx.get_option("fv.csr_walk") == 0
     opt_face_form = ctx.get_option("pcg.face_form") != 0
     hexw = hexd[0] > 0 and opt_face_hex
-    cells_total = m.n_cells * world
-    value = cells_total * args.steps / el
     # HBM bytes per launch from the PMC passes committed under profiles/ (scripts/pmc_traffic.sh +
     # scripts/pmc_summary.py: (2 FETCH_SIZE + WRITE_SIZE) KB, gfx950 correction), same workload
     pmc = {}
@@ -852,23 +912,12 @@ def main():
                           "per_kernel_frac": {k: roofs[k]["frac"] for k in asm}} if asm and asm_ms > 0 else None)
     primary = args.kernel if args.kernel != "auto" else (max(hbm, key=lambda k: hbm[k]["total_ms"]) if hbm else None)
     out = {
-        "metric": "cell-updates/s (dfLowMachFoam outer iter)",
-        "value": value,
-        "unit": "cell-updates/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": el / args.steps * 1e3,
-        "ms_per_step_median": med,
+        **head,
         "ms_per_step_events": {"min": float(step_ms.min()) if step_ms.size else None,
                                "max": float(step_ms.max()) if step_ms.size else None,
                                "mean": float(step_ms.mean()) if step_ms.size else None,
                                "note": "HIP events on the context stream after every timed step (rank 0's; the "
                                        "median is the max over ranks); ms_per_step is the bracketed wall time / K"},
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
         "data": ("reference initial fields (examples/dfLowMachFoam/notorch/threeD_reactingTGV/H2/cvodeIntegrator/0, "
                  "64^3, committed as tests/golden/tgv64) tiled over a hex box generated in-process"
                  if args.init == "reference" else "synthetic analytic TGV on a hex box generated in-process"),
@@ -893,7 +942,6 @@ def main():
         "rooflines": {k: {kk: v[kk] for kk in ("bound", "unit", "peak", "achieved", "frac", "traffic", "algorithmic_bytes",
                                                "avg_us", "launches", "impl_bytes", "frac_impl", "flops_per_launch",
                                                "hbm_frac") if kk in v} for k, v in roofs.items()},
-        "solver_iters": {e: s[0] for e, s in stats.items()},
         "solver_work_roof_pass": work,
         "solver_work_run": {"system_iterations": {e: work_pre[e] + work[e] for e in work},
                             "time_steps": args.warmup + args.steps + args.roof_steps,

@@ -5,6 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 L=deepflame-dev_amd/libdfmi.so
 cp $L /tmp/libdfmi_a.so
+STEPS="${STEPS:-20} --full"   # the bench line below takes it after --steps: the roofline pass runs too, whose rooflines the summary prints
 for k in ${ORDER:-A1 B1 A2 B2}; do
   case $k in A*) cp /tmp/libdfmi_a.so $L ;; B*) cp ab/libdfmi_b.so $L ;; esac
   timeout -k 10 300 python3 bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu --no-flame --alt-steps 0 > gpurun_out/ab_lib_$k.log 2>&1

@@ -7,6 +7,7 @@ ok() { [ "$1" -eq 0 ] || [ "$1" -eq 1 ]; }
 timeout -k 10 ${TEST_TIMEOUT:-400} python -m pytest tests -m gpu -q ${PYTEST_ARGS} > gpurun_out/gpu_tests.log 2>&1
 rc=$?; echo "tests rc=$rc"; tail -30 gpurun_out/gpu_tests.log; ok $rc || exit $rc
 [ -n "$SKIP_BENCH" ] && exit 0
+BENCH_ARGS="--full ${BENCH_ARGS}"   # the whole line: rooflines, side configurations, CPU baseline
 timeout -k 10 ${BENCH_TIMEOUT:-300} python bench.py ${BENCH_ARGS} > gpurun_out/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; tail -5 gpurun_out/bench.log; [ $rc -eq 0 ] || exit $rc
 [ -n "$SKIP_PROF" ] && exit 0

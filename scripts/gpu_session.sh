@@ -6,6 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 ok() { [ "$1" -eq 0 ] || [ "$1" -eq 1 ]; }
+BENCH_ARGS="--full ${BENCH_ARGS}"   # the whole line: rooflines, side configurations, CPU baseline
 if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 ${TEST_TIMEOUT:-600} python -u -m pytest tests -m gpu -x -v -s --timeout 240 --timeout-method thread ${PYTEST_ARGS} > gpurun_out/gpu_tests.log 2>&1
   rc=$?; echo "tests rc=$rc"; tail -15 gpurun_out/gpu_tests.log; ok $rc || exit $rc
@@ -19,7 +20,7 @@ fi
 IFS=';' read -ra VS <<< "${VARIANTS}"
 for v in "${VS[@]}"; do
   [ -z "$v" ] && continue
-  name="${v%%:*}"; rest="${v#*:}"; envs="${rest%%:*}"; args="${rest#*:}"
+  name="${v%%:*}"; rest="${v#*:}"; envs="${rest%%:*}"; args="--full ${rest#*:}"
   ( for e in $(echo "$envs" | tr ',' ' '); do export "$e"; done
     timeout -k 10 300 python bench.py --no-cpu --no-flame $args > gpurun_out/bench_$name.log 2>&1 )
   rc=$?; echo "variant $name rc=$rc"

@@ -9,7 +9,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 L=deepflame-dev_amd/libdfmi.so
 cp $L /tmp/libdfmi_a.so
-B="python3 bench.py --steps 1 --warmup 1 --roof-steps 1 --no-cpu --no-flame --alt-steps 0"
+B="python3 bench.py --full --steps 1 --warmup 1 --roof-steps 1 --no-cpu --no-flame --alt-steps 0"
 for arm in ${ARMS:-A B}; do
   case $arm in A) cp /tmp/libdfmi_a.so $L ;; B) cp ab/libdfmi_b.so $L ;; esac
   timeout -s KILL 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --output-format csv \

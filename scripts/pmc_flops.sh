@@ -5,6 +5,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS}"   # the roofline pass's dispatches are the steady ones the summary reads
 PMC="SQ_INSTS_VALU_FLOPS_FP64 SQ_INSTS_VALU_FLOPS_FP64_TRANS SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 SQ_WAVES"
 timeout -k 10 400 rocprofv3 --pmc $PMC --output-format csv -d gpurun_out/pmc_flops -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu --no-flame --alt-steps 0 ${BENCH_ARGS} > gpurun_out/pmc_flops.log 2>&1
 rc=$?; echo "pmc flops rc=$rc"; [ $rc -eq 0 ] || exit $rc

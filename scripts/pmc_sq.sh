@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 tag=${TAG:-sq}
 # CMD: the profiled program (default: a short headline bench); it must start with the interpreter itself
-CMD=${CMD:-"python3 bench.py --steps 2 --warmup 1 --no-cpu --no-flame --roof-steps 1 ${BENCH_ARGS}"}
+CMD=${CMD:-"python3 bench.py --full --steps 2 --warmup 1 --no-cpu --no-flame --roof-steps 1 ${BENCH_ARGS}"}
 timeout -k 10 300 rocprofv3 --pmc $PMC --output-format csv -d gpurun_out/pmc_$tag -o run -- $CMD > gpurun_out/pmc_$tag.log 2>&1
 rc=$?; echo "pmc rc=$rc"; [ $rc -eq 0 ] || exit $rc
 f=$(find gpurun_out/pmc_$tag -name "*counter_collection.csv" | sort | tail -1)

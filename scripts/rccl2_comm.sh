@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 TAG=${TAG:-r06}
 for v in halo:0 ov:1; do
   name="${v%%:*}"; ov="${v#*:}"
-  DFMI_HALO_OVERLAP=$ov DFMI_RCCL_SPLIT_HOSTS=1 timeout -k 10 300 python3 bench.py --gpus 2 --n ${N:-128} --steps 3 \
+  DFMI_HALO_OVERLAP=$ov DFMI_RCCL_SPLIT_HOSTS=1 timeout -k 10 300 python3 bench.py --full --gpus 2 --n ${N:-128} --steps 3 \
     --warmup 1 --roof-steps 2 --no-cpu --no-flame --alt-steps 0 > gpurun_out/${TAG}_rccl2_$name.log 2>&1
   rc=$?; echo "$name rc=$rc"; [ $rc -eq 0 ] || exit $rc
   grep '^{' gpurun_out/${TAG}_rccl2_$name.log | tail -1 > gpurun_out/${TAG}_rccl2_$name.json

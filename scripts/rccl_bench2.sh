@@ -9,7 +9,7 @@ for v in ${VARS:-halo: bj:DFMI_OPTIONS=amg.halo_l0=0}; do
   name="${v%%:*}"; envs="${v#*:}"; port=$((port + 1))
   ( for e in $(echo "$envs" | tr ',' ' '); do export "$e"; done
     DFMI_RCCL_SPLIT_HOSTS=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-      --master-addr 127.0.0.1 --master-port $port bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu --no-flame \
+      --master-addr 127.0.0.1 --master-port $port bench.py --full --gpus 2 --steps 3 --warmup 1 --no-cpu --no-flame \
       --alt-steps 0 > gpurun_out/bench_rccl2_$name.log 2>&1 )
   rc=$?; echo "$name rc=$rc"; [ $rc -eq 0 ] || exit $rc
   python3 - "$name" <<'PY'
