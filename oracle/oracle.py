@@ -50,6 +50,46 @@ def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def ldu_system(mesh, ptypes, lower, upper, diag, source, ic, bc):
+    """The linear system A x = b of one assembled LDU matrix with its boundary coefficients, as COO
+    triplets (rows, cols, vals, b; entries of one (row, col) pair add) (fvMatrix::addBoundaryDiag /
+    addBoundarySource(source, false) and the coupled interfaces; what the library's solver rows hold):
+    D = diag + sum internalCoeffs over the cell's non-empty slots; row neighbour / col owner = lower, row
+    owner / col neighbour = upper; a coupled primary slot b contributes -boundaryCoeffs[b] against its
+    partner cell; rhs = source + sum boundaryCoeffs over the non-coupled, non-empty slots. `ptypes`: the
+    field's per-patch condition codes. Cyclic partners are local cells; processor slots (partner on another
+    rank) carry column -1 -- a single-domain mesh has none."""
+    m = mesh
+    C_ = m.n_cells
+    types = np.asarray(ptypes)
+    d = np.array(diag, dtype=np.float64)
+    b = np.array(source, dtype=np.float64)
+    bfc = m.boundary_arrays()[4].astype(np.int64)
+    off = np.concatenate([[0], np.cumsum([p.slots for p in m.patches])]).astype(np.int64)
+    cr, cc, cv = [], [], []
+    for pi, p in enumerate(m.patches):
+        t = types[pi]
+        if t == EMPTY or p.size == 0:
+            continue
+        sl = slice(off[pi], off[pi] + p.size)           # primary slots (a processor patch's first half)
+        c = bfc[sl]
+        np.add.at(d, c, np.asarray(ic)[sl])
+        if t in (CYCLIC, PROC, PROC_CYC):
+            if p.kind == "cyclic":
+                q = p.neighbour_patch
+                partner = bfc[off[q]:off[q] + p.size]
+            else:
+                partner = -np.ones(p.size, dtype=np.int64)
+            cr.append(c); cc.append(partner); cv.append(-np.asarray(bc, dtype=np.float64)[sl])
+        else:
+            np.add.at(b, c, np.asarray(bc)[sl])
+    ar = np.arange(C_, dtype=np.int64)
+    rows = np.concatenate([np.asarray(m.neighbour, dtype=np.int64), np.asarray(m.owner, dtype=np.int64), ar] + cr)
+    cols = np.concatenate([np.asarray(m.owner, dtype=np.int64), np.asarray(m.neighbour, dtype=np.int64), ar] + cc)
+    vals = np.concatenate([np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64), d] + cv)
+    return rows, cols, vals, b
+
+
 class Oracle:
     """Holds contiguous copies of every array the restatement reads or writes."""
 
@@ -212,54 +252,10 @@ class Oracle:
         self._run("orc_correct_bc", field.encode(), ("boundary_" + field).encode(), ("ptype_" + ptype).encode(), ncomp)
 
     # ---- exact linear solves of the assembled LDU systems
-    def _slot_info(self):
-        m = self.m
-        kinds = self._kind
-        sp_ = []
-        for pi, p in enumerate(m.patches):
-            sp_ += [pi] * p.slots
-        prim = []
-        for p in m.patches:
-            prim += [1] * p.size + ([0] * p.size if p.kind in ("processor", "processorCyclic") else [])
-        bfc = m.boundary_arrays()[4]
-        partner = -np.ones(m.n_boundary_slots, dtype=np.int64)
-        off = 0
-        offs = []
-        for p in m.patches:
-            offs.append(off); off += p.slots
-        for pi, p in enumerate(m.patches):
-            if p.kind == "cyclic":
-                q = p.neighbour_patch
-                partner[offs[pi]:offs[pi] + p.size] = bfc[offs[q]:offs[q] + p.size]
-        return np.array(sp_, dtype=np.int64), np.array(prim, dtype=bool), bfc.astype(np.int64), partner
-
     def solve_ldu(self, lower, upper, diag, source, ic, bc, ptype_name):
-        m = self.m
-        C_ = m.n_cells
-        types = np.asarray(self.ptypes[ptype_name])
-        slot_patch, prim, bfc, partner = self._slot_info()
-        d = diag.copy()
-        b = source.copy()
-        rows = [m.neighbour, m.owner]
-        cols = [m.owner, m.neighbour]
-        vals = [lower, upper]
-        cr, cc, cv = [], [], []
-        for bslot in range(m.n_boundary_slots):
-            if not prim[bslot]:
-                continue
-            t = types[slot_patch[bslot]]
-            if t == EMPTY:
-                continue
-            c = bfc[bslot]
-            d[c] += ic[bslot]
-            if t in (CYCLIC, PROC, PROC_CYC):
-                cr.append(c); cc.append(partner[bslot]); cv.append(-bc[bslot])
-            else:
-                b[c] += bc[bslot]
-        A = sp.coo_matrix((np.concatenate(vals + [d, np.array(cv)]),
-                           (np.concatenate(rows + [np.arange(C_), np.array(cr, dtype=np.int64)]),
-                            np.concatenate(cols + [np.arange(C_), np.array(cc, dtype=np.int64)]))),
-                          shape=(C_, C_)).tocsc()
+        C_ = self.m.n_cells
+        rows, cols, vals, b = ldu_system(self.m, self.ptypes[ptype_name], lower, upper, diag, source, ic, bc)
+        A = sp.coo_matrix((vals, (rows, cols)), shape=(C_, C_)).tocsc()
         if C_ <= 5000:
             return spla.spsolve(A, b)
         # large meshes: a direct factorisation of a 3-D operator fills in badly; a Jacobi-preconditioned
