@@ -1123,6 +1123,13 @@ int dfmi_amg_info(dfmi_ctx* ctx, int max_levels, int* n_levels, int* cells, int*
     for (int l = 0; l < (int)x.amg.size() && l < max_levels; ++l) { cells[l] = x.amg[l].n; width[l] = x.amg[l].W; }
   });
 }
+// the V-cycle here smooths with weighted Jacobi only (amg.smoother is a GPU-library option)
+int dfmi_amg_smoother_info(dfmi_ctx*, int, double*, double*, long) {
+  return guard([&] { throw Error("dfmi (CPU-A): V-cycle inspection is a GPU-path feature"); });
+}
+int dfmi_amg_apply(dfmi_ctx*, const double*, double*, long) {
+  return guard([&] { throw Error("dfmi (CPU-A): V-cycle inspection is a GPU-path feature"); });
+}
 int dfmi_row_classes(dfmi_ctx*, int* n) {   // explicit CSR rows on the CPU
   if (n) *n = 0;
   return 0;

@@ -19,6 +19,13 @@ struct AmgLevel {
   DevBuf<float> fval, fD, fb, fx, fr, fxo;
   DevBuf<double> r2, zt;                // level 0 with l0_sweeps > 1: second residual, post-sweep ping-pong
   DevBuf<float> fr2;
+  // multicolour DILU (Amg::dilu): colour of every row, the rows listed colour by colour (crow[coff[c] .. coff[c+1])
+  // is colour c, ascending), and the factor E of the operator the sweeps read, in the V-cycle's precision
+  int ncol = 0;
+  std::vector<int> coff;                // host: colour offsets [ncol + 1]
+  DevBuf<int> colour, crow, dcoff;
+  DevBuf<double> E;
+  DevBuf<float> fE;
 };
 
 // Precision of the V-cycle (amg.precision). fp32 (default) keeps every level's operator and work vectors in single
@@ -34,6 +41,17 @@ struct Amg {
   double overcorr = 1.35;  // coarse-correction scaling (plain aggregation under-corrects; 1 = plain V-cycle)
   int coarse_sweeps = 8;
   int l0_sweeps = 1;       // weighted-Jacobi sweeps before and after the coarse correction on level 0
+  // amg.smoother = 1: multicolour DILU, M = (E + L) E^-1 (E + U) with L / U the couplings to lower / higher
+  // colours (amgxpOptions smoother=MULTICOLOR_DILU) in place of weighted Jacobi. Rank-local on every level; the
+  // Jacobi-only fusions (face-form / fused level 0, k_smooth_res_r8, k_vtail, k_pcg_small) are bypassed.
+  bool dilu = false;
+  DevBuf<double> dilu_bad;  // [1] set by the factor kernels when some E_i <= 0 (read with the solve's scalars)
+  // the level-0 operator the last build's V-cycle reads, for dfmi_amg_apply: the solver's workspace in the fp64
+  // Jacobi V-cycle (valid only until the next solve writes it: ws_gen), an owned copy otherwise
+  const double* val0_last = nullptr;
+  const double* D0_last = nullptr;
+  const long* ws_gen_p = nullptr;
+  long ws_gen = -1;
   bool padded = false;     // levels 1 .. L-2 in aligned groups of 8 per aggregate (pad_levels)
   bool tail = false;       // levels L-2 and L-1 of the fp32 V-cycle in one workgroup (k_vtail)
   int coarsest = 4096;
@@ -112,5 +130,11 @@ void amg_apply(Ctx& x, const double* val0, const double* D0, ColView col0, const
 // the level-0 first sweep (x0, residual) can be written by the PCG update kernel instead (linsolve.hip:
 // k_cg_x_smooth): fp32 V-cycle, launch-per-level path, one pre-sweep, at least two levels
 bool amg_l0_fusable(const Ctx& x);
+// amg.smoother = 1 asked for (before or after amg_setup): the p solve then takes the batched path at any size
+bool amg_dilu_wanted(const Ctx& x);
+// inspection (dfmi_amg_smoother_info / dfmi_amg_apply, one rank, after the first p solve)
+void amg_smoother_info(Ctx& x, int level, double* colour, double* dilu_diag, long count);
+void amg_apply_host(Ctx& x, const double* r, double* z, long count);
+const char* amg_not_m_matrix();   // the error raised when a DILU factor E_i <= 0 was seen (Amg::dilu_bad)
 
 }  // namespace dfmi

@@ -15,6 +15,8 @@
 // with one post-sweep; the coarsest level (<= 4096 cells) is
 // smoothed by a fixed number of Jacobi sweeps inside one workgroup (LDS-resident vectors). All pieces
 // are linear and the pre/post sweeps are adjoint, so the preconditioner is symmetric (valid for CG).
+// Option amg.smoother = 1 replaces the weighted-Jacobi sweeps on every level by a multicolour DILU
+// (amgxpOptions smoother=MULTICOLOR_DILU; the k_dilu_* kernels and apply_dilu_t below), default off.
 // Precision: by default the whole V-cycle runs in fp32 (operators rounded once per solve, work
 // vectors in float; AmgX's mixed-precision mode) -- it only preconditions, the PCG residuals, dot
 // products and solution stay fp64 -- which halves the preconditioner's bytes per iteration.
@@ -462,6 +464,226 @@ __global__ void __launch_bounds__(CTPB) k_vtail(int n, int W_, const int* __rest
   }
 }
 
+// ---------------------------------------------------------------- multicolour DILU (Amg::dilu, amg.smoother = 1)
+// M = (E + L) E^-1 (E + U): L / U are the couplings of a row to rows of a lower / higher colour, E the diagonal
+// factor E_i = D_i - sum_{j in L(i)} a_ij a_ji / E_j. PRECONDITION: the operator is symmetric (a_ji = a_ij -- the p
+// matrix and its Galerkin operators), so a row's own stored couplings stand for its column's and M is symmetric:
+// the V-cycle with the same M before and after the coarse correction stays a symmetric preconditioner for PCG.
+// Rows of one colour share no coupling, so one colour is one parallel pass; columns >= n (other ranks) are
+// dropped on every level (block DILU). ELL padding repeats the row's own cell, which is never of a lower or
+// higher colour than itself. The rows stay in the level's own order (AmgLevel::crow lists them per colour).
+//
+// All kernels walk the rows crow[r0 .. r1) of ONE colour c grid-strided; a single-workgroup launch instead loops
+// over the colours with a barrier between them (levels of <= DILU_SMALL_N cells: every colour in one launch).
+constexpr int DILU_SMALL_N = 4096;
+
+template <class T>
+__device__ __forceinline__ void dilu_factor_rows(int n, int W, const int* __restrict__ col, const T* __restrict__ val,
+                                                 const T* __restrict__ D, const int* __restrict__ colour,
+                                                 const int* __restrict__ crow, int r0, int r1, int c, T* E,
+                                                 double* bad, int t0, int stride) {
+  for (int t = r0 + t0; t < r1; t += stride) {
+    const int i = crow[t];
+    T e = D[i];
+    if (c > 0)
+      for (int k = 0; k < W; ++k) {
+        const int j = col[(long)k * n + i];
+        if (j < n && colour[j] < c) { const T a = val[(long)k * n + i]; e -= a * a / E[j]; }
+      }
+    E[i] = e;
+    if (!(e > (T)0)) *bad = 1.0;   // not an M-matrix: reported with the solve's scalars (record_stats)
+  }
+}
+// colours [c0, c1): more than one colour needs a grid of ONE block
+template <class T>
+__global__ void __launch_bounds__(CTPB) k_dilu_factor(int n, int W, const int* __restrict__ col,
+                                                      const T* __restrict__ val, const T* __restrict__ D,
+                                                      const int* __restrict__ colour, const int* __restrict__ crow,
+                                                      const int* __restrict__ coff, int c0, int c1, T* E, double* bad) {
+  const int t0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+  for (int c = c0; c < c1; ++c) {
+    dilu_factor_rows<T>(n, W, col, val, D, colour, crow, coff[c], coff[c + 1], c, E, bad, t0, stride);
+    if (c + 1 < c1) __syncthreads();
+  }
+}
+
+// forward pass of colour c: v_i = (src_i - sum_{colour j < c} a_ij v_j) / E_i (src may be v itself: a row reads its
+// own entry and finished lower colours only). With `out` (the LAST colour, whose backward step is the identity):
+// out_i = y_i + v_i (y may be out). Returns this thread's share of bdot . out.
+template <int WT, class T, class TB, class TO>
+__device__ __forceinline__ double dilu_fwd_rows(int n, int W_, const int* __restrict__ col, const T* __restrict__ val,
+                                                const T* __restrict__ E, const int* __restrict__ colour,
+                                                const int* __restrict__ crow, int r0, int r1, int c, const TB* src,
+                                                T* v, const T* y, TO* out, const double* bdot, int t0, int stride) {
+  const int W = WT > 0 ? WT : W_;
+  double acc = 0.0;
+  for (int t = r0 + t0; t < r1; t += stride) {
+    const int i = crow[t];
+    T s = (T)src[i];
+    if (c > 0) {
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        const int j = col[(long)k * n + i];
+        if (j < n && colour[j] < c) s -= val[(long)k * n + i] * v[j];
+      }
+    }
+    s = s / E[i];
+    v[i] = s;
+    if (out) {
+      const TO o = (TO)(y[i] + s);
+      out[i] = o;
+      if (bdot) acc += bdot[i] * (double)o;
+    }
+  }
+  return acc;
+}
+// backward pass of colour c: v_i = v_i - (sum_{colour j > c} a_ij v_j) / E_i, in place; `out` as above
+template <int WT, class T, class TO>
+__device__ __forceinline__ double dilu_bwd_rows(int n, int W_, const int* __restrict__ col, const T* __restrict__ val,
+                                                const T* __restrict__ E, const int* __restrict__ colour,
+                                                const int* __restrict__ crow, int r0, int r1, int c, T* v, const T* y,
+                                                TO* out, const double* bdot, int t0, int stride) {
+  const int W = WT > 0 ? WT : W_;
+  double acc = 0.0;
+  for (int t = r0 + t0; t < r1; t += stride) {
+    const int i = crow[t];
+    T s = 0;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const int j = col[(long)k * n + i];
+      if (j < n && colour[j] > c) s += val[(long)k * n + i] * v[j];
+    }
+    const T vi = v[i] - s / E[i];
+    v[i] = vi;
+    if (out) {
+      const TO o = (TO)(y[i] + vi);
+      out[i] = o;
+      if (bdot) acc += bdot[i] * (double)o;
+    }
+  }
+  return acc;
+}
+// r = b - A y over the rows t0, t0 + stride, ...; with agg: y = x + sc P xc is formed here and stored to yo
+template <int WT, class T, class TB>
+__device__ __forceinline__ void dilu_res_rows(int n, int W_, const int* __restrict__ col, const T* __restrict__ val,
+                                              const T* __restrict__ D, const TB* b, const T* x,
+                                              const int* __restrict__ agg, const T* xc, T sc, T* yo, T* r, int t0,
+                                              int stride) {
+  const int W = WT > 0 ? WT : W_;
+  for (int i = t0; i < n; i += stride) {
+    const T yi = agg ? x[i] + sc * xc[agg[i]] : x[i];
+    T ay = D[i] * yi;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const int j = col[(long)k * n + i];
+      if (j < n) ay += val[(long)k * n + i] * (agg ? x[j] + sc * xc[agg[j]] : x[j]);
+    }
+    if (agg) yo[i] = yi;
+    r[i] = (T)b[i] - ay;
+  }
+}
+
+// block partials of a pass that wrote `out`: pmode 1 stores, 2 adds (the passes of one application run one after
+// another on the stream, every one on the same grid, so the sum is formed in a fixed order)
+__device__ __forceinline__ void dilu_partial(double acc, double* partial, int pmode) {
+  __shared__ double sh[TPB / 64];
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0;
+    for (int w = 0; w < TPB / 64; ++w) a += sh[w];
+    if (pmode == 1) partial[blockIdx.x] = a; else partial[blockIdx.x] += a;
+  }
+}
+
+template <int WT, class T, class TB, class TO>
+__global__ void __launch_bounds__(TPB) k_dilu_fwd(int n, int W_, const int* __restrict__ col,
+                                                  const T* __restrict__ val, const T* __restrict__ E,
+                                                  const int* __restrict__ colour, const int* __restrict__ crow, int r0,
+                                                  int r1, int c, const TB* src, T* v, const T* y, TO* out,
+                                                  const double* bdot, double* partial, int pmode, const double* act) {
+  if (act && *act == 0.0) return;   // uniform
+  const double acc = dilu_fwd_rows<WT, T, TB, TO>(n, W_, col, val, E, colour, crow, r0, r1, c, src, v, y, out, bdot,
+                                                  blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+  if (pmode) dilu_partial(acc, partial, pmode);
+}
+template <int WT, class T, class TO>
+__global__ void __launch_bounds__(TPB) k_dilu_bwd(int n, int W_, const int* __restrict__ col,
+                                                  const T* __restrict__ val, const T* __restrict__ E,
+                                                  const int* __restrict__ colour, const int* __restrict__ crow, int r0,
+                                                  int r1, int c, T* v, const T* y, TO* out, const double* bdot,
+                                                  double* partial, int pmode, const double* act) {
+  if (act && *act == 0.0) return;   // uniform
+  const double acc = dilu_bwd_rows<WT, T, TO>(n, W_, col, val, E, colour, crow, r0, r1, c, v, y, out, bdot,
+                                              blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+  if (pmode) dilu_partial(acc, partial, pmode);
+}
+template <int WT, class T, class TB>
+__global__ void __launch_bounds__(TPB) k_dilu_res(int n, int W_, const int* __restrict__ col,
+                                                  const T* __restrict__ val, const T* __restrict__ D, const TB* b,
+                                                  const T* x, const int* __restrict__ agg, const T* xc, T sc, T* yo,
+                                                  T* r, const double* act) {
+  if (act && *act == 0.0) return;
+  dilu_res_rows<WT, T, TB>(n, W_, col, val, D, b, x, agg, xc, sc, yo, r, blockIdx.x * blockDim.x + threadIdx.x,
+                           gridDim.x * blockDim.x);
+}
+
+// A level of <= DILU_SMALL_N cells in ONE workgroup, the colours separated by barriers (global memory: one
+// workgroup's stores are visible to it after the barrier). mode 0, pre-smoothing from zero: x = M^-1 b, r = b - A x.
+// mode 1, post-smoothing: xo = x + sc P xc, xo += M^-1 (b - A xo). mode 2, the coarsest level: x = M^-1 b, then
+// sweeps - 1 times x += M^-1 (b - A x); out = x.
+template <int WT, class T, class TB, class TO>
+__global__ void __launch_bounds__(CTPB) k_dilu_small(int mode, int n, int W_, const int* __restrict__ col,
+                                                     const T* __restrict__ val, const T* __restrict__ D,
+                                                     const T* __restrict__ E, const int* __restrict__ colour,
+                                                     const int* __restrict__ crow, const int* __restrict__ coff,
+                                                     int ncol, const TB* b, T* x, T* r, T* xo, TO* out,
+                                                     const int* __restrict__ agg, const T* xc, T sc, int sweeps,
+                                                     const double* act) {
+  if (act && *act == 0.0) return;   // uniform: every barrier below is reached by the whole workgroup or by none
+  const int t0 = threadIdx.x, stride = CTPB;
+  // v = M^-1 src (src may be v)
+  auto minv = [&](const auto* src, T* v) {
+    for (int c = 0; c < ncol; ++c) {
+      dilu_fwd_rows<WT, T, std::remove_cv_t<std::remove_pointer_t<decltype(src)>>, T>(
+          n, W_, col, val, E, colour, crow, coff[c], coff[c + 1], c, src, v, nullptr, (T*)nullptr, nullptr, t0, stride);
+      __syncthreads();
+    }
+    for (int c = ncol - 2; c >= 0; --c) {
+      dilu_bwd_rows<WT, T, T>(n, W_, col, val, E, colour, crow, coff[c], coff[c + 1], c, v, nullptr, (T*)nullptr,
+                              nullptr, t0, stride);
+      __syncthreads();
+    }
+  };
+  T* cur = x;
+  int steps = 0;
+  if (mode == 1) {
+    cur = xo;
+    steps = 1;
+    dilu_res_rows<WT, T, TB>(n, W_, col, val, D, b, x, agg, xc, sc, xo, r, t0, stride);
+    __syncthreads();
+  } else {
+    minv(b, x);
+    steps = mode == 2 ? sweeps - 1 : 0;
+    if (steps > 0 || mode == 0) {
+      dilu_res_rows<WT, T, TB>(n, W_, col, val, D, b, x, nullptr, nullptr, sc, nullptr, r, t0, stride);
+      __syncthreads();
+    }
+  }
+  for (int s = 0; s < steps; ++s) {   // cur += M^-1 r, r = b - A cur for the next step
+    minv((const T*)r, r);
+    for (int i = t0; i < n; i += stride) cur[i] += r[i];
+    __syncthreads();
+    if (s + 1 < steps) {
+      dilu_res_rows<WT, T, TB>(n, W_, col, val, D, b, cur, nullptr, nullptr, sc, nullptr, r, t0, stride);
+      __syncthreads();
+    }
+  }
+  if (mode == 2 && (const void*)out != (const void*)x)
+    for (int i = t0; i < n; i += stride) out[i] = (TO)x[i];
+}
+
 // ---------------------------------------------------------------- agglomerated coarsest level (Amg::global)
 // rank's packed rows (nmax rows of wg values + the diagonal): local coarsest couplings (slots < wloc of the
 // level's own ELL; up to wc), the external couplings summed in double from the level-0 halo coefficients
@@ -699,6 +921,9 @@ void amg_setup(Ctx& x) {
   a.coarsest = std::min(COARSEST, std::max(8, (int)x.opt("amg.coarsest_size")));
   a.overcorr = x.opt("amg.overcorrection");
   a.fp32 = x.opt("amg.precision") != 64;
+  a.dilu = amg_dilu_wanted(x);
+  DFMI_CHECK(!(a.dilu && x.on("amg.global_coarse")),
+             "amg.smoother = 1 (multicolour DILU) is rank-local on every level: not with amg.global_coarse = 1");
   const int C = x.C;
   // level 0: the solver ELL (columns >= C are halo entries, dropped in the preconditioner)
   std::vector<int> col((size_t)x.ell.W * C);
@@ -771,25 +996,83 @@ void amg_setup(Ctx& x) {
       if (l == 0 && a.l0_sweeps > 1) v.r2.alloc(nv);
     }
     if (l == 0 && a.l0_sweeps > 1) v.zt.alloc(nv);
+    if (a.dilu) {
+      // colours from the level's final columns (after pad_levels' renumbering); the factor E beside the operator
+      // it belongs to -- in fp64 level 0 keeps its own copy of the solver's rows, so that a reused V-cycle
+      // (amg.reuse, amg.reuse_steps) never pairs E with the values of a later solve
+      std::vector<int> lc;
+      if (l > 0) {
+        lc.resize(ne);
+        DFMI_HIP(hipMemcpy(lc.data(), v.col.p, ne * sizeof(int), hipMemcpyDeviceToHost));
+      }
+      std::vector<int> cl;
+      v.ncol = colour_rows(l > 0 ? lc : col, v.W, v.n, cl);
+      v.coff.assign(v.ncol + 1, 0);
+      for (int i = 0; i < v.n; ++i) v.coff[cl[i] + 1]++;
+      for (int c = 0; c < v.ncol; ++c) v.coff[c + 1] += v.coff[c];
+      std::vector<int> rows(nv), pos(v.coff.begin(), v.coff.end() - 1);
+      for (int i = 0; i < v.n; ++i) rows[pos[cl[i]]++] = i;
+      v.colour.upload(cl, x.stream);
+      v.crow.upload(rows, x.stream);
+      v.dcoff.upload(v.coff, x.stream);
+      DFMI_HIP(hipStreamSynchronize(x.stream));
+      if (a.fp32) v.fE.alloc(nv);
+      else {
+        v.E.alloc(nv);
+        if (l == 0) { v.val.alloc(ne); v.D.alloc(nv); }
+      }
+    }
   }
+  if (a.dilu) { a.dilu_bad.alloc(1); a.dilu_bad.zero(x.stream); }
   if (want_global) global_setup(x, col, fin_aggs, last_col);
   // measured (in-process ranks of 64^3): p-iterations per solve 14 / 17 / 19 -> 12 / 14 / 14-15 for 2 / 4 / 8
   // ranks (one rank: 12) for two more halo exchanges per PCG iteration; amg.halo_l0 = 0: block-Jacobi
-  a.halo_l0 = x.nranks > 1 && halo_active(x) && x.on("amg.halo_l0") && a.lv.size() >= 2 && a.l0_sweeps == 1;
+  a.halo_l0 = x.nranks > 1 && halo_active(x) && x.on("amg.halo_l0") && a.lv.size() >= 2 && a.l0_sweeps == 1 && !a.dilu;
   if (a.halo_l0) a.hy.alloc((size_t)C + x.H);
   // the last two levels as one single-workgroup launch (k_vtail; amg.tail = 0: the launch chain)
   {
     const int L = (int)a.lv.size();
     a.tail = x.on("amg.tail") && a.padded && a.fp32 && L >= 3 && a.lv[L - 2].n <= TAIL_N &&
              a.lv[L - 2].n % 8 == 0 && a.lv[L - 2].W <= TAIL_W && a.lv[L - 1].n <= COARSEST &&
-             (size_t)a.lv[L - 1].n * a.lv[L - 1].W <= LDS_ENT && !a.global;
+             (size_t)a.lv[L - 1].n * a.lv[L - 1].W <= LDS_ENT && !a.global && !a.dilu;
   }
   a.ready = true;
 }
 
 // Per solve: coarse operators from the level-0 values (val0 [W][C], D0 = diag + internalCoeffs).
+namespace {
+// explicit ELL columns of level l (level 0: the solver's)
+const int* dilu_col(Ctx& x, int l) { return l == 0 ? (const int*)x.ell.col.p : (const int*)x.amg.lv[l].col.p; }
+// the DILU factor of level l from the values just built (E is rebuilt exactly when they are)
+template <class T>
+void dilu_factor(Ctx& x, int l, const T* val, const T* D, T* E) {
+  AmgLevel& v = x.amg.lv[l];
+  KScope _ks(x, "k_dilu_factor");
+  if (v.n <= DILU_SMALL_N)
+    hipLaunchKernelGGL(k_dilu_factor<T>, dim3(1), dim3(CTPB), 0, x.stream, v.n, v.W, dilu_col(x, l), val, D,
+                       (const int*)v.colour.p, (const int*)v.crow.p, (const int*)v.dcoff.p, 0, v.ncol, E,
+                       x.amg.dilu_bad.p);
+  else
+    for (int c = 0; c < v.ncol; ++c)
+      hipLaunchKernelGGL(k_dilu_factor<T>, dim3(blocks_for(v.coff[c + 1] - v.coff[c], TPB)), dim3(TPB), 0, x.stream, v.n,
+                         v.W, dilu_col(x, l), val, D, (const int*)v.colour.p, (const int*)v.crow.p,
+                         (const int*)v.dcoff.p, c, c + 1, E, x.amg.dilu_bad.p);
+  DFMI_HIP(hipGetLastError());
+}
+}  // namespace
+
 void amg_galerkin(Ctx& x, const double* val0, const double* D0) {
   Amg& a = x.amg;
+  a.val0_last = val0;
+  a.D0_last = D0;
+  a.ws_gen_p = &x.sws().gen;
+  a.ws_gen = x.sws().gen;
+  if (a.dilu && !a.fp32) {   // fp64 DILU: level 0 sweeps read their own copy of this build's rows
+    AmgLevel& l0 = a.lv[0];
+    DFMI_HIP(hipMemcpyAsync(l0.val.p, val0, (size_t)l0.W * l0.n * sizeof(double), hipMemcpyDeviceToDevice, x.stream));
+    DFMI_HIP(hipMemcpyAsync(l0.D.p, D0, (size_t)l0.n * sizeof(double), hipMemcpyDeviceToDevice, x.stream));
+    dilu_factor<double>(x, 0, l0.val.p, l0.D.p, l0.E.p);
+  }
   if (a.fp32) {   // the level-0 smoother reads a single-precision copy of the solver's ELL operator
     AmgLevel& l0 = a.lv[0];
     KScope _ks(x, "k_round_f32");
@@ -806,6 +1089,7 @@ void amg_galerkin(Ctx& x, const double* val0, const double* D0) {
     }
     hipLaunchKernelGGL(k_round_f32, dim3(512), dim3(TPB), 0, x.stream, (long)l0.n, D0, l0.fD.p);
     DFMI_HIP(hipGetLastError());
+    if (a.dilu) dilu_factor<float>(x, 0, l0.fval.p, l0.fD.p, l0.fE.p);
   }
   for (size_t l = 0; l + 1 < a.lv.size(); ++l) {
     AmgLevel& f = a.lv[l];
@@ -822,6 +1106,10 @@ void amg_galerkin(Ctx& x, const double* val0, const double* D0) {
       hipLaunchKernelGGL((k_galerkin<float, float>), g, dim3(TPB), 0, x.stream, c.n, c.W + 1, f.gstart.p, f.gsrc.p,
                          (const float*)f.fval.p, (const float*)f.fD.p, c.fval.p, c.fD.p);
     DFMI_HIP(hipGetLastError());
+    if (a.dilu) {
+      if (a.fp32) dilu_factor<float>(x, (int)l + 1, c.fval.p, c.fD.p, c.fE.p);
+      else dilu_factor<double>(x, (int)l + 1, c.val.p, c.D.p, c.E.p);
+    }
   }
   if (a.global) {   // the agglomerated level: pack this rank's rows, all-gather, unpack (identical on every rank)
     AmgLevel& c = a.lv.back();
@@ -1008,6 +1296,133 @@ void apply_t(Ctx& x, const double* val0, const double* D0, ColView col0, const d
   DFMI_HIP(hipGetLastError());
 }
 
+// The V-cycle with the multicolour DILU smoother (amg.smoother = 1), z = V(r) and the block partials of r.z.
+// Pre-smoothing from zero x = M^-1 b, r = b - A x, restriction; the coarsest level amg.coarsest_sweeps
+// applications from zero; prolongation with the over-correction, then x += M^-1 (b - A x) -- the same symmetric M
+// on both sides of the coarse correction. Level 0 and levels above DILU_SMALL_N cells take one launch per colour
+// pass (forward colours 0 .. nc-1, backward nc-2 .. 0: the last colour's backward step is the identity) and one
+// for the residual; smaller levels run a whole smoothing step in one workgroup (k_dilu_small). The pass that
+// finishes a row of the post-smoothing also writes x + M^-1(..) for it (level 0: z and the partials of r.z).
+// None of the Jacobi fusions (k_smooth_res_r8, k_vtail, the fused level-0 sweep) is used; amg.omega is unused.
+template <class T>
+void apply_dilu_t(Ctx& x, const int* col0, const double* r, double* z, double* partial, int nblk, const double* act) {
+  constexpr bool F = std::is_same<T, float>::value;
+  Amg& a = x.amg;
+  const int L = (int)a.lv.size();
+  const T sc = (T)a.overcorr;
+  hipStream_t st = x.stream;
+  auto VAL = [&](int l) -> const T* { if constexpr (F) return a.lv[l].fval.p; else return a.lv[l].val.p; };
+  auto DD = [&](int l) -> const T* { if constexpr (F) return a.lv[l].fD.p; else return a.lv[l].D.p; };
+  auto EE = [&](int l) -> const T* { if constexpr (F) return a.lv[l].fE.p; else return a.lv[l].E.p; };
+  auto COL = [&](int l) { return l == 0 ? col0 : (const int*)a.lv[l].col.p; };
+  auto BV = [&](int l) -> T* { if constexpr (F) return a.lv[l].fb.p; else return a.lv[l].b.p; };
+  auto XV = [&](int l) -> T* { if constexpr (F) return a.lv[l].fx.p; else return a.lv[l].x.p; };
+  auto RV = [&](int l) -> T* { if constexpr (F) return a.lv[l].fr.p; else return a.lv[l].r.p; };
+  auto XO = [&](int l) -> T* { if constexpr (F) return a.lv[l].fxo.p; else return a.lv[l].xo.p; };
+  auto CLR = [&](int l) { return (const int*)a.lv[l].colour.p; };
+  auto ROW = [&](int l) { return (const int*)a.lv[l].crow.p; };
+  auto small = [&](int l) { return l > 0 && a.lv[l].n <= DILU_SMALL_N; };
+  // v = M^-1 src on level l (src may be v), one launch per colour pass. With `out`: out = y + v, written by the
+  // pass that finishes each row; with `part` too (level 0) every pass runs on the nblk-block grid and the passes
+  // that write out leave the block partials of bdot . out
+  auto minv = [&](int l, const auto* src, T* v, const T* y, auto* out, const double* bdot, double* part) {
+    using TB = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
+    using TO = std::remove_pointer_t<decltype(out)>;
+    AmgLevel& f = a.lv[l];
+    for (int c = 0; c < f.ncol; ++c) {
+      const bool last = c == f.ncol - 1;
+      const dim3 g(part ? nblk : blocks_for(f.coff[c + 1] - f.coff[c], TPB));
+      KScope _ks(x, "k_dilu_fwd");
+      launch_w(f.W, g, st, k_dilu_fwd<0, T, TB, TO>, k_dilu_fwd<6, T, TB, TO>, f.n, f.W, COL(l), VAL(l), EE(l), CLR(l),
+               ROW(l), f.coff[c], f.coff[c + 1], c, src, v, y, last ? out : (TO*)nullptr, bdot, part,
+               part && last ? 1 : 0, act);
+    }
+    for (int c = f.ncol - 2; c >= 0; --c) {
+      const dim3 g(part ? nblk : blocks_for(f.coff[c + 1] - f.coff[c], TPB));
+      KScope _ks(x, "k_dilu_bwd");
+      launch_w(f.W, g, st, k_dilu_bwd<0, T, TO>, k_dilu_bwd<6, T, TO>, f.n, f.W, COL(l), VAL(l), EE(l), CLR(l), ROW(l),
+               f.coff[c], f.coff[c + 1], c, v, y, out, bdot, part, part ? 2 : 0, act);
+    }
+    DFMI_HIP(hipGetLastError());
+  };
+  // r = b - A y on level l; with agg: y = x + sc P xc formed on the way and stored to yo
+  auto resid = [&](int l, const auto* b, const T* xv, const int* agg, const T* xc, T* yo, T* rv) {
+    using TB = std::remove_cv_t<std::remove_pointer_t<decltype(b)>>;
+    AmgLevel& f = a.lv[l];
+    KScope _ks(x, "k_dilu_res");
+    launch_w(f.W, dim3(blocks_for(f.n, TPB)), st, k_dilu_res<0, T, TB>, k_dilu_res<6, T, TB>, f.n, f.W, COL(l), VAL(l),
+             DD(l), b, xv, agg, xc, sc, yo, rv, act);
+    DFMI_HIP(hipGetLastError());
+  };
+  // a whole smoothing step of a small level in one workgroup (mode: k_dilu_small)
+  auto one_wg = [&](int mode, int l, const auto* b, T* xv, T* rv, T* xo, auto* out, const int* agg, const T* xc) {
+    using TB = std::remove_cv_t<std::remove_pointer_t<decltype(b)>>;
+    using TO = std::remove_pointer_t<decltype(out)>;
+    AmgLevel& f = a.lv[l];
+    KScope _ks(x, "k_dilu_small");
+    if (f.W == 6)
+      hipLaunchKernelGGL((k_dilu_small<6, T, TB, TO>), dim3(1), dim3(CTPB), 0, st, mode, f.n, f.W, COL(l), VAL(l), DD(l),
+                         EE(l), CLR(l), ROW(l), (const int*)f.dcoff.p, f.ncol, b, xv, rv, xo, out, agg, xc, sc,
+                         a.coarse_sweeps, act);
+    else
+      hipLaunchKernelGGL((k_dilu_small<0, T, TB, TO>), dim3(1), dim3(CTPB), 0, st, mode, f.n, f.W, COL(l), VAL(l), DD(l),
+                         EE(l), CLR(l), ROW(l), (const int*)f.dcoff.p, f.ncol, b, xv, rv, xo, out, agg, xc, sc,
+                         a.coarse_sweeps, act);
+    DFMI_HIP(hipGetLastError());
+  };
+  const T* nullT = nullptr;
+  T* nullO = nullptr;
+  // down
+  for (int l = 0; l < L - 1; ++l) {
+    AmgLevel& f = a.lv[l];
+    if (small(l)) {
+      one_wg(0, l, (const T*)BV(l), XV(l), RV(l), nullO, nullO, nullptr, nullT);
+    } else if (l == 0) {
+      minv(0, r, XV(0), nullT, nullO, nullptr, nullptr);
+      resid(0, r, XV(0), nullptr, nullT, nullO, RV(0));
+      for (int s = 1; s < a.l0_sweeps; ++s) {   // further applications: x += M^-1 r, the residual formed again
+        minv(0, (const T*)RV(0), RV(0), (const T*)XV(0), XV(0), nullptr, nullptr);
+        resid(0, r, XV(0), nullptr, nullT, nullO, RV(0));
+      }
+    } else {
+      minv(l, (const T*)BV(l), XV(l), nullT, nullO, nullptr, nullptr);
+      resid(l, (const T*)BV(l), XV(l), nullptr, nullT, nullO, RV(l));
+    }
+    KScope _ks(x, "k_restrict");
+    hipLaunchKernelGGL(k_restrict<T>, dim3(blocks_for(a.lv[l + 1].n, TPB)), dim3(TPB), 0, st, a.lv[l + 1].n, f.mstart.p,
+                       f.members.p, (const T*)RV(l), BV(l + 1), act, CgStop{});
+    DFMI_HIP(hipGetLastError());
+  }
+  // coarsest
+  if (L > 1) {
+    one_wg(2, L - 1, (const T*)BV(L - 1), XV(L - 1), RV(L - 1), nullO, XV(L - 1), nullptr, nullT);
+  } else if constexpr (!F) {   // a single level (double only) smooths straight into z
+    one_wg(2, 0, r, XV(0), RV(0), nullO, z, nullptr, nullT);
+    KScope _ks(x, "k_dot_partial");
+    hipLaunchKernelGGL(k_dot_partial, dim3(nblk), dim3(TPB), 0, st, x.C, r, (const double*)z, partial);
+  }
+  // up
+  for (int l = L - 2; l >= 0; --l) {
+    AmgLevel& f = a.lv[l];
+    if (small(l)) {
+      one_wg(1, l, (const T*)BV(l), XV(l), RV(l), XO(l), nullO, (const int*)f.agg.p, (const T*)XV(l + 1));
+    } else if (l > 0) {
+      resid(l, (const T*)BV(l), XV(l), (const int*)f.agg.p, (const T*)XV(l + 1), XO(l), RV(l));
+      minv(l, (const T*)RV(l), RV(l), (const T*)XO(l), XO(l), nullptr, nullptr);
+    } else {
+      resid(0, r, XV(0), (const int*)f.agg.p, (const T*)XV(1), XO(0), RV(0));
+      for (int s = 1; s < a.l0_sweeps; ++s) {
+        minv(0, (const T*)RV(0), RV(0), (const T*)XO(0), XO(0), nullptr, nullptr);
+        resid(0, r, XO(0), nullptr, nullT, nullO, RV(0));
+      }
+      minv(0, (const T*)RV(0), RV(0), (const T*)XO(0), z, r, partial);
+    }
+    // the corrected x of this level feeds the next finer prolongation
+    if (l > 0) { if constexpr (F) std::swap(f.fx, f.fxo); else std::swap(f.x, f.xo); }
+  }
+  DFMI_HIP(hipGetLastError());
+}
+
 }  // namespace
 
 namespace {
@@ -1042,7 +1457,14 @@ AmgView<double> amg_view_f64(Ctx& x, const double* val0, const double* D0, const
 
 bool amg_l0_fusable(const Ctx& x) {
   const Amg& a = x.amg;
-  return a.fp32 && a.lv.size() >= 2 && a.l0_sweeps == 1;
+  // DILU: none of the Jacobi-only level-0 fusions (pcg.fuse_l0, the face-form level 0, the novals shortcut)
+  return a.fp32 && a.lv.size() >= 2 && a.l0_sweeps == 1 && !a.dilu;
+}
+
+bool amg_dilu_wanted(const Ctx& x) {
+  const double v = x.opt("amg.smoother");
+  DFMI_CHECK(v == 0.0 || v == 1.0, "amg.smoother must be 0 (weighted Jacobi) or 1 (multicolour DILU)");
+  return v == 1.0;
 }
 
 void amg_apply(Ctx& x, const double* val0, const double* D0, ColView col0, const double* r, double* z,
@@ -1050,8 +1472,78 @@ void amg_apply(Ctx& x, const double* val0, const double* D0, ColView col0, const
   Amg& a = x.amg;
   DFMI_CHECK(!l0_done || amg_l0_fusable(x), "AMG: level-0 sweep fused on an unsupported configuration");
   CommTag _ct(x, x.comm.tag + " amg");
+  if (a.dilu) {
+    if (a.fp32) apply_dilu_t<float>(x, col0.col, r, z, partial, nblk, active);
+    else apply_dilu_t<double>(x, col0.col, r, z, partial, nblk, active);
+    return;
+  }
   if (a.fp32) apply_t<float>(x, val0, D0, col0, r, z, partial, nblk, active, l0_done, stop);
   else apply_t<double>(x, val0, D0, col0, r, z, partial, nblk, active, l0_done, stop);
 }
+
+// ---------------------------------------------------------------- inspection (no reference counterpart)
+namespace {
+const char* const NOT_M_MATRIX = "p operator is not an M-matrix; use amg.smoother = 0";
+void inspect_checks(Ctx& x, const char* who) {
+  const Amg& a = x.amg;
+  DFMI_CHECK(a.ready && a.val0_last, std::string(who) + ": valid after the first p solve with the AMG preconditioner");
+  DFMI_CHECK(x.nranks == 1, std::string(who) + ": one rank only");
+  DFMI_HIP(hipStreamSynchronize(x.stream));
+}
+// the fp64 Jacobi V-cycle reads level 0 straight from the solver's workspace: current only until the next solve
+void check_l0_current(const Ctx& x, const char* who) {
+  const Amg& a = x.amg;
+  DFMI_CHECK(a.fp32 || a.dilu || (a.ws_gen_p && *a.ws_gen_p == a.ws_gen),
+             std::string(who) + ": the fp64 V-cycle reads level 0 from the solver's rows and a later solve has "
+             "overwritten them (set amg.reuse = 0 and ask right after the p solve)");
+}
+template <class T>
+void download_widen(const T* dev, double* host, long n) {
+  std::vector<T> h((size_t)n);
+  DFMI_HIP(hipMemcpy(h.data(), dev, (size_t)n * sizeof(T), hipMemcpyDeviceToHost));
+  for (long i = 0; i < n; ++i) host[i] = (double)h[i];
+}
+}  // namespace
+
+void amg_smoother_info(Ctx& x, int level, double* colour, double* dilu_diag, long count) {
+  inspect_checks(x, "dfmi_amg_smoother_info");
+  Amg& a = x.amg;
+  DFMI_CHECK(level >= 0 && level < (int)a.lv.size(), "dfmi_amg_smoother_info: no such level");
+  AmgLevel& v = a.lv[level];
+  DFMI_CHECK(count == v.n, "dfmi_amg_smoother_info: count must be the level's cell count (dfmi_amg_info)");
+  if (a.dilu) {
+    double bad = 0.0;
+    DFMI_HIP(hipMemcpy(&bad, a.dilu_bad.p, sizeof(double), hipMemcpyDeviceToHost));
+    DFMI_CHECK(bad == 0.0, NOT_M_MATRIX);
+    download_widen<int>(v.colour.p, colour, count);
+    if (a.fp32) download_widen<float>(v.fE.p, dilu_diag, count);
+    else download_widen<double>(v.E.p, dilu_diag, count);
+    return;
+  }
+  std::fill(colour, colour + count, 0.0);
+  if (a.fp32) download_widen<float>(v.fD.p, dilu_diag, count);
+  else if (level > 0) download_widen<double>(v.D.p, dilu_diag, count);
+  else {
+    check_l0_current(x, "dfmi_amg_smoother_info");
+    download_widen<double>(a.D0_last, dilu_diag, count);
+  }
+}
+
+void amg_apply_host(Ctx& x, const double* r, double* z, long count) {
+  inspect_checks(x, "dfmi_amg_apply");
+  check_l0_current(x, "dfmi_amg_apply");
+  Amg& a = x.amg;
+  DFMI_CHECK(count == x.C, "dfmi_amg_apply: count must be the cell count");
+  const int nblk = std::min(blocks_for(count, TPB), 1024);
+  DevBuf<double> dr, dz, dp;
+  dr.upload(r, (size_t)count, x.stream);
+  dz.alloc((size_t)count);
+  dp.alloc((size_t)nblk);
+  amg_apply(x, a.val0_last, a.D0_last, x.ell.cols(), dr.p, dz.p, dp.p, nblk);
+  DFMI_HIP(hipMemcpyAsync(z, dz.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, x.stream));
+  DFMI_HIP(hipStreamSynchronize(x.stream));
+}
+
+const char* amg_not_m_matrix() { return NOT_M_MATRIX; }
 
 }  // namespace dfmi

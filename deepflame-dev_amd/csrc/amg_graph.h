@@ -164,6 +164,47 @@ inline void amg_level_data(const std::vector<int>& fcol, int Wf, int nf, int nc,
   if (r.gsrc.empty()) r.gsrc.push_back(0);
 }
 
+// Colouring of a level for the multicolour DILU smoother (ELL columns col [W][n]; columns >= n are other ranks'
+// cells and ignored, padding repeats the row's own cell): no two coupled rows share a colour. Greedy in row
+// order -- every row takes the lowest colour none of its coloured neighbours has -- so a 7-point box in
+// lexicographic (or 2x2x2-nested) order with even periodic dimensions gets the two colours of its checkerboard,
+// and rows without couplings (padding rows) colour 0. Where that leaves more than two colours (an odd periodic
+// dimension closes the checkerboard on itself and plain greedy then spends two extra colours on the seam) the
+// greedy pass is repeated with the rows grouped by their colour, highest colour first (Culberson's iterated
+// greedy: a pass over whole colour classes never needs more colours than before), while the count still drops.
+// Deterministic. Returns the colour count; colour[i] in [0, count).
+inline int colour_rows(const std::vector<int>& col, int W, int n, std::vector<int>& colour) {
+  auto pass = [&](const std::vector<int>& order, std::vector<int>& out) {
+    out.assign(n, -1);
+    std::vector<int> mark(W + 2, -1);   // a row has at most W neighbours: a colour <= W is always free
+    int nc = 0;
+    for (int v : order) {
+      for (int k = 0; k < W; ++k) {
+        const int j = col[(size_t)k * n + v];
+        if (j < n && j != v && out[j] >= 0) mark[out[j]] = v;
+      }
+      int c = 0;
+      while (mark[c] == v) ++c;
+      out[v] = c;
+      nc = std::max(nc, c + 1);
+    }
+    return nc;
+  };
+  std::vector<int> order(n);
+  std::iota(order.begin(), order.end(), 0);
+  int nc = pass(order, colour);
+  for (int it = 0; it < 8 && nc > 2; ++it) {
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return colour[a] > colour[b]; });
+    std::vector<int> next;
+    const int m = pass(order, next);
+    if (m >= nc) break;
+    nc = m;
+    colour.swap(next);
+    std::iota(order.begin(), order.end(), 0);
+  }
+  return nc;
+}
+
 inline AmgCoarse amg_coarsen(const std::vector<int>& fcol, int Wf, int nf, const Graph& g, int passes = 3) {
   AmgCoarse r;
   // `passes` pairwise passes -> aggregates of up to 2^passes cells (3: 2x2x2 on a hex mesh)

@@ -1071,6 +1071,14 @@ int dfmi_amg_info(dfmi_ctx* ctx, int max_levels, int* n_levels, int* cells, int*
   });
 }
 
+int dfmi_amg_smoother_info(dfmi_ctx* ctx, int level, double* colour, double* dilu_diag, long count) {
+  return guard([&] { amg_smoother_info(ctx->x, level, colour, dilu_diag, count); });
+}
+
+int dfmi_amg_apply(dfmi_ctx* ctx, const double* r, double* z, long count) {
+  return guard([&] { amg_apply_host(ctx->x, r, z, count); });
+}
+
 int dfmi_row_classes(dfmi_ctx* ctx, int* n) {
   return guard([&] { *n = ctx->x.ell.ready ? ctx->x.ell.ncls : 0; });
 }
@@ -1092,12 +1100,19 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
     static const char* structural_keys[] = {"amg.omega", "amg.overcorrection", "amg.coarsest_sweeps",
                                             "amg.coarsest_size", "amg.presweeps", "amg.pairwise_passes_l0",
                                             "amg.pairwise_passes", "amg.precision", "amg.padded", "amg.tail",
-                                            "amg.halo_l0", "amg.global_coarse", "solver.even_odd", "solver.small",
+                                            "amg.halo_l0", "amg.global_coarse", "amg.smoother", "solver.even_odd", "solver.small",
                                             "solver.row_classes"};
     bool structural = false;
     for (const char* s : structural_keys) structural |= k == s;
     DFMI_CHECK(!structural || (!x.amg.ready && !x.ell.ready),
                "dfmi_set_option: '" + k + "' shapes the solver structures; set it before the first solve");
+    DFMI_CHECK(k != "amg.smoother" || value == 0.0 || value == 1.0,
+               "dfmi_set_option: amg.smoother must be 0 (weighted Jacobi) or 1 (multicolour DILU)");
+    // multicolour DILU is rank-local on every level: no agglomerated coarsest level beside it
+    const bool dilu = k == "amg.smoother" ? value == 1.0 : x.opt("amg.smoother") == 1.0;
+    const bool global = k == "amg.global_coarse" ? value != 0.0 : x.on("amg.global_coarse");
+    DFMI_CHECK(!((k == "amg.smoother" || k == "amg.global_coarse") && dilu && global),
+               "dfmi_set_option: amg.smoother = 1 (multicolour DILU) and amg.global_coarse = 1 exclude each other");
     x.opts[k] = value;
   });
 }

@@ -257,6 +257,7 @@ inline const OptDef* option_defs(int& n) {
     {"amg.reuse_steps", 8},           // > 1: the first corrector reuses the V-cycle operators of up to this many - 1
                                       // earlier steps (1: rebuilt every step). 1 -> 8: 13.59 -> 13.42 ms per step, 3
                                       // rounds each, 674 against 678 p system-iterations in 28 steps (r06u)
+    {"amg.smoother", 0},              // 0: weighted Jacobi; 1: multicolour DILU (amgxpOptions smoother=MULTICOLOR_DILU)
     {"amg.reuse", 1},                 // later correctors of a time step precondition with the step's first V-cycle
                                       // operators (level-0 fp32 copy, Galerkin levels) instead of rebuilding them
     {"solver.even_odd", 1},           // U/Y/E: BiCGStab on the even-odd Schur complement where the rows 2-colour
@@ -376,6 +377,7 @@ struct Ctx {
     DevBuf<int> sysmap;
     HostRecs poll;                   // convergence records the device posts (linsolve.hip: Poller)
     long long poll_seq = 0;          // records posted so far
+    long gen = 0;                    // bumped whenever a solve or an assembly rewrites buf (Amg::ws_gen)
   } ws, ws_y;
   // the YEqn batch has its own solver workspace (its rows are assembled while the UEqn solve may still be
   // running on the other stream, dfmi_time_step); linsolve.hip reaches the current one through sws()

@@ -37,6 +37,7 @@ inline int eo_max_blocks() { return EO_BLOCKS; }
 inline int cg_max_blocks() { return MAX_BLOCKS; }
 constexpr int PAD = INT_MIN;
 constexpr int NSCAL = 16;
+constexpr int STAT_FLAG = NSCAL - 1;   // snapshot slot of the DILU factor's failure flag (Amg::dilu_bad; p only)
 
 static_assert(TPB == RED_TPB, "the fixed-order reductions (dfmi_common.h red_sum) assume 256-thread blocks");
 
@@ -1321,8 +1322,12 @@ int work_slot(const std::string& eqn) {
 
 // the solve's scalars stored straight into the mapped host snapshot (vector stores; one launch instead of a launch and
 // a copy), and its system-iterations summed into the equation's work counter
-__global__ void k_accum_iters(const double* scal, int nsys, double* acc, double* snap) {
+__global__ void k_accum_iters(const double* scal, int nsys, double* acc, double* snap, const double* flag) {
   for (int i = threadIdx.x; i < nsys * NSCAL; i += blockDim.x) snap[i] = scal[i];
+  if (flag) {   // the preconditioner's failure flag rides in the last (otherwise unused) slot of system 0
+    __syncthreads();
+    if (threadIdx.x == 0) snap[STAT_FLAG] = *flag;
+  }
   if (threadIdx.x != 0) return;
   double a = 0.0;
   for (int s = 0; s < nsys; ++s) a += scal[s * NSCAL + 7];
@@ -1331,12 +1336,12 @@ __global__ void k_accum_iters(const double* scal, int nsys, double* acc, double*
 
 // final state of the solve, recorded for dfmi_solver_stats without waiting (it synchronises before reading);
 // iterations summed into the equation's work counter on the device
-void record_stats(Ctx& x, const char* eqn, const double* scal, int nsys) {
+void record_stats(Ctx& x, const char* eqn, const double* scal, int nsys, const double* flag = nullptr) {
   if (x.work.n == 0) { x.work.alloc(4); x.work.zero(x.stream); }
   auto& sn = x.stat_snap[eqn];
   sn.h.ensure_mapped((size_t)nsys * NSCAL);
   sn.nsys = nsys;
-  hipLaunchKernelGGL(k_accum_iters, dim3(1), dim3(64), 0, x.stream, scal, nsys, x.work.p + work_slot(eqn), sn.h.d);
+  hipLaunchKernelGGL(k_accum_iters, dim3(1), dim3(64), 0, x.stream, scal, nsys, x.work.p + work_slot(eqn), sn.h.d, flag);
 }
 
 }  // namespace
@@ -1649,6 +1654,7 @@ void bicg_layout(Ctx& x, int nsys, double** val, double** dS, double** rhs) {
                       (size_t)nsys * std::max(nblk, eo_max_blocks()) * 12 + 64;
   if (x.sws().buf.n < need) { x.sws().buf.alloc(need); x.sws().buf.zero(x.stream); }   // no stale NaN under a 0 coefficient
   const long N = nsys * Ce;
+  ++x.sws().gen;
   *dS = x.sws().buf.p;
   *rhs = x.sws().buf.p + N;
   *val = x.sws().buf.p + BCG_VECS * N;
@@ -1720,6 +1726,8 @@ SolveStats solve_stats(Ctx& x, const std::string& eqn) {
   auto it = x.stat_snap.find(eqn);
   DFMI_CHECK(it != x.stat_snap.end(), "no solve recorded for " + eqn);
   DFMI_HIP(hipStreamSynchronize(x.stream));
+  // the DILU factor found some E_i <= 0 during a build this solve preconditioned with (flag copied by record_stats)
+  DFMI_CHECK(!(eqn == "p" && x.amg.dilu && it->second.h.p[STAT_FLAG] != 0.0), amg_not_m_matrix());
   SolveStats st;
   for (int s = 0; s < it->second.nsys; ++s) {   // worst system
     const double* h = it->second.h.p + s * NSCAL;
@@ -1750,6 +1758,7 @@ SolveStats solve_bicgstab(Ctx& x, const char* eqn, int nsys, const int* sys_map_
     smap = WS.sysmap.p;
   }
   const long N = nsys * Ce;
+  ++WS.gen;
   double* base = WS.buf.p;
   // U's three components share one operator: built and read once (k_ell_build vshared). Valid because every
   // coupled patch this library accepts is translational (cyclic / processor / processorCyclic: the generic
@@ -1935,6 +1944,7 @@ SolveStats solve_pcg(Ctx& x, const char* eqn, const double* lower, const double*
   const size_t need = 8 * Ce + (size_t)W * C + (size_t)nblk * 6 + 64;
   if (WS.buf.n < need) WS.buf.alloc(need);
   if (WS.scal.n < NSCAL) WS.scal.alloc(NSCAL);
+  ++WS.gen;
   double* base = WS.buf.p;
   CV v{base, base + Ce, base + 2 * Ce, base + 3 * Ce, base + 4 * Ce, base + 5 * Ce, base + 6 * Ce, base + 7 * Ce};
   double* val = base + 8 * Ce;
@@ -1947,6 +1957,9 @@ SolveStats solve_pcg(Ctx& x, const char* eqn, const double* lower, const double*
   dim3 g(nblk), bl(TPB);
   Launch L{x, nblk, 1};
   const bool amg = cfg.precond == 1;
+  // multicolour DILU (amg.smoother = 1): k_pcg_small's in-workgroup V-cycle is Jacobi-only, so the solve takes the
+  // batched path at any size
+  const bool small = small_solve(x) && !(amg && amg_dilu_wanted(x));
   // the symmetric p operator read face-wise on a hex box (FaceOp, one rank; pcg.face_form = 0: the ELL values)
   const bool face = x.hex[0] > 0 && x.fslot && x.nranks == 1 && !halo_active(x) && !small_solve(x) && x.on("pcg.face_form");
   // a later corrector of the same step (amg.reuse): the V-cycle keeps the operators the first corrector built --
@@ -1974,7 +1987,8 @@ SolveStats solve_pcg(Ctx& x, const char* eqn, const double* lower, const double*
     }
   }
   halo_vecs(x, {v.xw}, 1, Ce);
-  if (small_solve(x)) {
+  const double* pflag = amg && x.amg.dilu ? (const double*)x.amg.dilu_bad.p : nullptr;
+  if (small) {
     dispatch_W(W, [&](auto wt) {
       constexpr int WT = decltype(wt)::value;
       KScope _ks(x, "k_pcg_small");
@@ -1991,7 +2005,7 @@ SolveStats solve_pcg(Ctx& x, const char* eqn, const double* lower, const double*
       }
     });
     DFMI_HIP(hipGetLastError());
-    record_stats(x, eqn, WS.scal.p, 1);
+    record_stats(x, eqn, WS.scal.p, 1, pflag);
     return SolveStats{};
   }
   dispatch_W(W, [&](auto wt) {
@@ -2039,7 +2053,7 @@ SolveStats solve_pcg(Ctx& x, const char* eqn, const double* lower, const double*
       if (it >= cfg.max_iter) break;
       if (poll.after(it)) break;
     }
-    record_stats(x, eqn, WS.scal.p, 1);
+    record_stats(x, eqn, WS.scal.p, 1, pflag);
     return SolveStats{};
   }
   // (r.z, r.r) readers: Jacobi -> both from q2; AMG -> r.z from the V-cycle's partials in q3
@@ -2111,7 +2125,7 @@ SolveStats solve_pcg(Ctx& x, const char* eqn, const double* lower, const double*
     if (poll.after(it)) break;
   }
   DFMI_HIP(hipGetLastError());
-  record_stats(x, eqn, WS.scal.p, 1);
+  record_stats(x, eqn, WS.scal.p, 1, pflag);
   return SolveStats{};
 }
 

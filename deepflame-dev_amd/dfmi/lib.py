@@ -70,6 +70,8 @@ SIGNATURES = {
     "dfmi_set_preconditioner": [_P, C.c_char_p, C.c_char_p],
     "dfmi_set_option": [_P, C.c_char_p, C.c_double], "dfmi_get_option": [_P, C.c_char_p, _DP],
     "dfmi_amg_info": [_P, C.c_int, _IP, _IP, _IP],
+    "dfmi_amg_smoother_info": [_P, C.c_int, _DP, _DP, C.c_long],
+    "dfmi_amg_apply": [_P, _DP, _DP, C.c_long],
     "dfmi_row_classes": [_P, _IP],
     "dfmi_hex_dims": [_P, _IP, _IP, _IP],
     "dfmi_correct_boundary": [_P, C.c_char_p],
@@ -381,6 +383,23 @@ class Context:
         n = C.c_int(); cells = np.zeros(32, np.int32); w = np.zeros(32, np.int32)
         self._call("dfmi_amg_info", self.h, 32, C.byref(n), _ip(cells), _ip(w))
         return [(int(cells[i]), int(w[i])) for i in range(n.value)]
+
+    def amg_smoother_info(self, level: int):
+        """(colour, dilu_diag) of every row of an AMG level after the first p solve (one rank): the row's colour and
+        the DILU factor E of the level's current operator (amg.smoother = 1), or zeros and the level's diagonal
+        (amg.smoother = 0). Inspection aid in the role of get_matrix; no reference counterpart."""
+        n = self.amg_info()[level][0]
+        colour = np.zeros(n); diag = np.zeros(n)
+        self._call("dfmi_amg_smoother_info", self.h, int(level), _dp(colour), _dp(diag), n)
+        return colour.astype(np.int64), diag
+
+    def amg_apply(self, r):
+        """z = V-cycle(r) with the hierarchy and operators of the last p solve's build (one rank, either smoother;
+        launch-per-level path). Inspection aid; no reference counterpart."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        z = np.zeros_like(r)
+        self._call("dfmi_amg_apply", self.h, _dp(r), _dp(z), r.size)
+        return z
 
     def row_classes(self):
         """distinct gather-row classes decoded per cell (0: explicit ELL columns)"""

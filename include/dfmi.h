@@ -195,7 +195,9 @@ int dfmi_set_preconditioner(dfmi_ctx* ctx, const char* eqn, const char* name);
 /* implementation options by key (the role of the reference's amgx*Options files, e.g.
  * examples/dfLowMachFoam/notorch/threeD_reactingTGV/H2/cvodeIntegrator/system/amgxpOptions:1-18, and of the
  * CanteraTorchProperties switches): "amg.*" (omega, overcorrection, coarsest_sweeps, coarsest_size,
- * presweeps, pairwise_passes_l0, pairwise_passes, precision 32|64, padded, tail, halo_l0, global_coarse),
+ * presweeps, pairwise_passes_l0, pairwise_passes, precision 32|64, padded, tail, halo_l0, global_coarse,
+ * smoother 0 weighted Jacobi | 1 multicolour DILU -- amgxpOptions "smoother=MULTICOLOR_DILU"; any other value is
+ * refused, and so is 1 together with global_coarse),
  * "solver.*" (even_odd, small, row_classes), "pcg.*" (face_form, fuse_l0), "fv.*" (hex_walk, csr_walk,
  * species_generic, yprep_brick), "chem.*" (method 0 ROS3 | 1 extrapolation, generated, binning),
  * "dnn.tuned_gemm"; keys and
@@ -205,6 +207,18 @@ int dfmi_get_option(dfmi_ctx* ctx, const char* key, double* value);
 /* AMG hierarchy after the first p solve: level count, cells and ELL width per level (with several ranks
  * and the option amg.global_coarse the agglomerated coarsest level of all ranks is listed last) */
 int dfmi_amg_info(dfmi_ctx* ctx, int max_levels, int* n_levels, int* cells, int* width);
+/* Inspection of the p preconditioner, in the role of dfmi_get_matrix (no reference counterpart: AmgX keeps its
+ * smoother data to itself). Both are valid after the first p solve with the AMG preconditioner, on one rank, and
+ * fail cleanly otherwise.
+ * dfmi_amg_smoother_info: the colour of every row of `level` (as doubles; count = the level's cells, dfmi_amg_info)
+ * and, with amg.smoother = 1, the DILU factor E of that level's current operator, in the V-cycle's precision
+ * widened to double; with amg.smoother = 0 colour is all zero and dilu_diag the level's diagonal.
+ * dfmi_amg_apply: z = V-cycle(r) (count = cells) with the hierarchy and operators of the last build, through the
+ * launch-per-level path (no PCG fusion), either smoother. The fp64 Jacobi V-cycle reads level 0 from the solver's
+ * rows: there the call (and level 0 of dfmi_amg_smoother_info) fails once a later solve has overwritten them
+ * -- set amg.reuse = 0 and call right after the p solve; stale values are never read. */
+int dfmi_amg_smoother_info(dfmi_ctx* ctx, int level, double* colour, double* dilu_diag, long count);
+int dfmi_amg_apply(dfmi_ctx* ctx, const double* r, double* z, long count);
 /* gather-row classes in use (0: explicit columns): after the first solve, the number of distinct
  * (column offset, coefficient source) rows the solver / assembly gathers decode from one byte per cell
  * instead of reading 2 W ints (hex boxes in blockMesh order: 27). Measurement aid (no reference
