@@ -1236,6 +1236,7 @@ int dfmi_dnn_load_model(dfmi_ctx*, const char*, double, double) {
 }
 int dfmi_dnn_infer(dfmi_ctx*, int*) { return guard([&] { throw Error("dfmi (CPU-A): DNN chemistry is a GPU-path feature"); }); }
 int dfmi_dnn_stats(dfmi_ctx*, int*, double*) { return guard([&] { throw Error("dfmi (CPU-A): DNN chemistry is a GPU-path feature"); }); }
+int dfmi_dnn_plan(dfmi_ctx*, int, int*, int*) { return guard([&] { throw Error("dfmi (CPU-A): DNN chemistry is a GPU-path feature"); }); }
 int dfmi_kernel_timer(dfmi_ctx*, const char*) { return guard([&] { throw Error("dfmi (CPU-A): no kernels"); }); }
 int dfmi_kernel_time(dfmi_ctx*, double*, int*) { return guard([&] { throw Error("dfmi (CPU-A): no kernels"); }); }
 int dfmi_kernel_time_named(dfmi_ctx*, const char*, double*, int*) { return guard([&] { throw Error("dfmi (CPU-A): no kernels"); }); }

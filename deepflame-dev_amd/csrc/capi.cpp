@@ -977,6 +977,12 @@ int dfmi_dnn_load_model(dfmi_ctx* ctx, const char* path, double T_react, double 
       DFMI_CHECK(dims[l] > 0 && dims[l] <= 65536 && dims[l + 1] > 0 && dims[l + 1] <= 65536, std::string(path) + ": bad widths");
       np += (size_t)dims[l] * dims[l + 1] + dims[l + 1];
     }
+    // the size the header implies against the file, before anything is sized from the header (widths <= 2^16 and
+    // <= 8 layers keep np below 2^36, n_modules <= 63: no product here can wrap a 64-bit size_t, checked anyway)
+    static_assert(sizeof(size_t) >= 8, "64-bit size_t expected");
+    DFMI_CHECK(np <= (size_t)1 << 40, std::string(path) + ": bad widths");
+    const size_t implied = o + 8 * (2 * (size_t)dims[0] + 2 * (size_t)nmod) + 4 * np * (size_t)nmod;
+    DFMI_CHECK(implied <= raw.size(), std::string("truncated DF-ODENet model file ") + path);
     xmu.resize(dims[0]); xstd.resize(dims[0]); ymu.resize(nmod); ystd.resize(nmod);
     take(xmu.data(), 8 * xmu.size()); take(xstd.data(), 8 * xstd.size());
     take(ymu.data(), 8 * ymu.size()); take(ystd.data(), 8 * ystd.size());
@@ -1006,6 +1012,13 @@ int dfmi_dnn_stats(dfmi_ctx* ctx, int* n_reacting, double* gemm_flops) {
     if (n_reacting) *n_reacting = d.last_reacting;
     if (gemm_flops) *gemm_flops = d.gemm_flops;
     d.gemm_flops = 0;
+  });
+}
+
+int dfmi_dnn_plan(dfmi_ctx* ctx, int max_layers, int* n_layers, int* kinds) {
+  return guard([&] {
+    DFMI_CHECK(n_layers && (kinds || max_layers <= 0), "null output");
+    dnn_plan(ctx->x, max_layers, n_layers, kinds);
   });
 }
 

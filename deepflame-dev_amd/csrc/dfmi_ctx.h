@@ -542,6 +542,7 @@ void dnn_upload(Ctx& x, int nmod, int nlayers, const int* dims, const float* par
 double hbm_copy_gbs(Ctx& x, size_t bytes, int reps);   // measured device copy bandwidth (fv_kernels.hip)
 void dnn_prepare(Ctx& x);   // reacting-cell compaction + count read-back, ahead of dnn_solve
 void dnn_solve(Ctx& x, const char* rho_field);   // RR scaled by rho_field (reference: d_rho_old, dfYEqn.cu:449)
+void dnn_plan(Ctx& x, int max_layers, int* n_layers, int* kinds);   // the kernel form dnn_solve takes per hidden layer
 // chem.hip
 void chem_upload(Ctx& x, int R, const int* idata, const int* irs, const double* dd);
 // rho_field: the thermo density RR is scaled by (dfChemistryModel.C:771, problem.rhoi = rho_[celli]);

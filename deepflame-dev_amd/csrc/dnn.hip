@@ -835,6 +835,32 @@ void dnn_prepare(Ctx& x) {
   d.prepared = true;
 }
 
+// The kernel form of hidden layer l (0 <= l < L - 1), the one place the choice is made (dnn_solve launches by it,
+// dnn_plan reports it): 0 k_mlp_gemm, 1 k_mlp_gemm_in (K == 64), 2 k_mlp_gemm_pp (K % 64 == 0, K and N >= 512),
+// 3 k_mlp_gemm_pp with two 16-column tail strips (N = 256 q + t, q >= 2, 0 < t <= 32, the row stride of the output
+// within the strips' zero fill), 4 k_mlp_gemm with the output layer fused (the last hidden layer), 5 k_mlp_gemm_pp
+// with the output layer fused (the last hidden layer, K % 64 == 0 and K >= 512). tuned = 0: 0 and 4 only.
+static int dnn_layer_kind(const Dnn& d, int l, bool tuned) {
+  const int L = (int)d.dims.size() - 1;
+  const int N = d.dims[l + 1], K = d.Kp[l], ldc = d.Kp[l + 1];
+  if (l + 2 == L) return tuned && K % 64 == 0 && K >= 512 ? 5 : 4;
+  if (tuned && K % 64 == 0 && K >= 512 && N >= 512) {
+    const bool tail = N % 256 != 0 && N % 256 <= 32 && ldc <= N / 256 * 256 + 64 && N / 256 >= 2;
+    return tail ? 3 : 2;
+  }
+  if (tuned && K == 64) return 1;
+  return 0;
+}
+
+void dnn_plan(Ctx& x, int max_layers, int* n_layers, int* kinds) {
+  const Dnn& d = x.dnn;
+  DFMI_CHECK(d.ready, "DNN model not set (dfmi_dnn_set_model)");
+  const int L = (int)d.dims.size() - 1;
+  const bool tuned = x.on("dnn.tuned_gemm");
+  *n_layers = L - 1;
+  for (int l = 0; l + 1 < L && l < max_layers; ++l) kinds[l] = dnn_layer_kind(d, l, tuned);
+}
+
 void dnn_solve(Ctx& x, const char* rho_field) {
   Dnn& d = x.dnn;
   DFMI_CHECK(d.ready, "DNN model not set (dfmi_dnn_set_model)");
@@ -873,7 +899,7 @@ void dnn_solve(Ctx& x, const char* rho_field) {
     // the last hidden layer by the ping-pong kernel where its K allows (four 64-column partials per 256-wide
     // tile) or by k_mlp_gemm (two per 128-wide tile): partial sums per row of the fused output layer
     const bool tuned = x.on("dnn.tuned_gemm");
-    const bool pp_out = tuned && d.Kp[L - 2] % 64 == 0 && d.Kp[L - 2] >= 512;
+    const bool pp_out = dnn_layer_kind(d, L - 2, tuned) == 5;
     const int nq = pp_out ? 4 * blocks_for(d.dims[L - 1], 256) : 2 * blocks_for(d.dims[L - 1], BN);
     const long sP = (long)nq * n;
     if (d.part.n < (size_t)d.nmod * sP) d.part.alloc((size_t)d.nmod * sP);
@@ -883,34 +909,37 @@ void dnn_solve(Ctx& x, const char* rho_field) {
       d.gemm_flops += 2.0 * n * N * d.dims[l] * d.nmod;   // algorithmic flops (unpadded K)
       const dim3 g(blocks_for(N, BN) * blocks_for(n, 256), 1, d.nmod);
       KScope _ks(x, "k_mlp_gemm");
-      if (l + 2 == L) {   // last hidden layer: the output layer fused into the epilogue
-        d.gemm_flops += 2.0 * n * N * d.nmod;
-        if (pp_out)
+      switch (dnn_layer_kind(d, l, tuned)) {
+        case 5:   // last hidden layer: the output layer fused into the epilogue
+          d.gemm_flops += 2.0 * n * N * d.nmod;
           hipLaunchKernelGGL((k_mlp_gemm_pp<true, true>), dim3(blocks_for(N, 256) * blocks_for(n, 256), 1, d.nmod),
                              dim3(512), 0, x.stream, n, N, K, in, lda, sIn, d.W[l].p, (long)N * K, d.b[l].p, (long)N, out,
                              ldc, (long)n * ldc, d.W[L - 1].p, (long)d.Kp[L - 1], d.part.p, sP);
-        else
+          break;
+        case 4:
+          d.gemm_flops += 2.0 * n * N * d.nmod;
           hipLaunchKernelGGL((k_mlp_gemm<true, true>), g, dim3(256), 0, x.stream, n, N, K, in, lda, sIn, d.W[l].p,
                              (long)N * K, d.b[l].p, (long)N, out, ldc, (long)n * ldc, d.W[L - 1].p, (long)d.Kp[L - 1],
                              d.part.p, sP);
-      } else if (tuned && K % 64 == 0 && K >= 512 && N >= 512) {   // the 1600 -> 800 layer
-        const dim3 gw(blocks_for(N, 256) * blocks_for(n, 256), 1, d.nmod);
-        // N = 256 q + t, 0 < t <= 16 q: q tiles, the last two with 16-column tail strips
-        const bool tail = N % 256 != 0 && N % 256 <= 32 && ldc <= N / 256 * 256 + 64 && N / 256 >= 2;
-        const dim3 gt(N / 256 * blocks_for(n, 256), 1, d.nmod);
-        if (tail)
-          hipLaunchKernelGGL((k_mlp_gemm_pp<true, false, 16>), gt, dim3(512), 0, x.stream, n, N, K, in, lda, sIn,
-                             d.W[l].p, (long)N * K, d.b[l].p, (long)N, out, ldc, (long)n * ldc, nullptr, 0L, nullptr, 0L);
-        else
-          hipLaunchKernelGGL((k_mlp_gemm_pp<true>), gw, dim3(512), 0, x.stream, n, N, K, in, lda, sIn, d.W[l].p,
-                             (long)N * K, d.b[l].p, (long)N, out, ldc, (long)n * ldc);
-      } else if (tuned && K == 64) {   // the 55 -> 1600 input layer of the 53-species nets
-        hipLaunchKernelGGL((k_mlp_gemm_in<true, 128>), dim3(blocks_for(N, 128) * blocks_for(n, 128), 1, d.nmod),
-                           dim3(256), 0, x.stream, n, N, K, in, lda, sIn, d.W[l].p, (long)N * K, d.b[l].p, (long)N, out,
-                           ldc, (long)n * ldc);
-      } else {
-        hipLaunchKernelGGL((k_mlp_gemm<true, false>), g, dim3(256), 0, x.stream, n, N, K, in, lda, sIn, d.W[l].p,
-                           (long)N * K, d.b[l].p, (long)N, out, ldc, (long)n * ldc, nullptr, 0L, nullptr, 0L);
+          break;
+        case 3:   // N = 256 q + t, 0 < t <= 32: q tiles, the last two with 16-column tail strips (the 800-wide layer)
+          hipLaunchKernelGGL((k_mlp_gemm_pp<true, false, 16>), dim3(N / 256 * blocks_for(n, 256), 1, d.nmod), dim3(512), 0,
+                             x.stream, n, N, K, in, lda, sIn, d.W[l].p, (long)N * K, d.b[l].p, (long)N, out, ldc,
+                             (long)n * ldc, nullptr, 0L, nullptr, 0L);
+          break;
+        case 2:   // the 1600 -> 800 layer's kernel without strips
+          hipLaunchKernelGGL((k_mlp_gemm_pp<true>), dim3(blocks_for(N, 256) * blocks_for(n, 256), 1, d.nmod), dim3(512), 0,
+                             x.stream, n, N, K, in, lda, sIn, d.W[l].p, (long)N * K, d.b[l].p, (long)N, out, ldc,
+                             (long)n * ldc);
+          break;
+        case 1:   // the 55 -> 1600 input layer of the 53-species nets
+          hipLaunchKernelGGL((k_mlp_gemm_in<true, 128>), dim3(blocks_for(N, 128) * blocks_for(n, 128), 1, d.nmod),
+                             dim3(256), 0, x.stream, n, N, K, in, lda, sIn, d.W[l].p, (long)N * K, d.b[l].p, (long)N, out,
+                             ldc, (long)n * ldc);
+          break;
+        default:
+          hipLaunchKernelGGL((k_mlp_gemm<true, false>), g, dim3(256), 0, x.stream, n, N, K, in, lda, sIn, d.W[l].p,
+                             (long)N * K, d.b[l].p, (long)N, out, ldc, (long)n * ldc, nullptr, 0L, nullptr, 0L);
       }
       DFMI_HIP(hipGetLastError());
       in = out;

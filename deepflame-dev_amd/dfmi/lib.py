@@ -93,6 +93,7 @@ SIGNATURES = {
     "dfmi_dnn_load_model": [_P, C.c_char_p, C.c_double, C.c_double],
     "dfmi_dnn_infer": [_P, _IP],
     "dfmi_dnn_stats": [_P, _IP, _DP],
+    "dfmi_dnn_plan": [_P, C.c_int, _IP, _IP],
 }
 
 
@@ -378,6 +379,14 @@ class Context:
         n = C.c_int(); f = C.c_double()
         self._call("dfmi_dnn_stats", self.h, C.byref(n), C.byref(f))
         return n.value, f.value
+
+    def dnn_plan(self):
+        """kernel form per hidden layer of the installed model under the current dnn.tuned_gemm (include/dfmi.h
+        dfmi_dnn_plan: 0 generic, 1 input-128, 2 ping-pong, 3 ping-pong with tail strips, 4 generic with the fused
+        output layer, 5 ping-pong with the fused output layer). Inspection aid; no reference counterpart."""
+        n = C.c_int(); kinds = np.zeros(8, np.int32)
+        self._call("dfmi_dnn_plan", self.h, 8, C.byref(n), _ip(kinds))
+        return [int(k) for k in kinds[:n.value]]
 
     def amg_info(self):
         n = C.c_int(); cells = np.zeros(32, np.int32); w = np.zeros(32, np.int32)

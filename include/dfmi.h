@@ -288,6 +288,12 @@ int dfmi_dnn_load_model(dfmi_ctx* ctx, const char* path, double T_react, double 
 int dfmi_dnn_infer(dfmi_ctx* ctx, int* n_reacting);
 /* reacting cells of the last inference; algorithmic hidden-layer GEMM flops since the last call */
 int dfmi_dnn_stats(dfmi_ctx* ctx, int* n_reacting, double* gemm_flops);
+/* the GEMM kernel form the next dfmi_dnn_infer takes for each hidden layer of the installed model under the current
+ * "dnn.tuned_gemm" (n_layers = Linear layers - 1; at most max_layers kinds written): 0 generic 256x128x32 ring,
+ * 1 128x128x64 input-layer kernel, 2 256x256x64 ping-pong, 3 ping-pong with two 16-column tail strips, 4 generic with
+ * the output layer fused, 5 ping-pong with the output layer fused. Inspection aid in the role of dfmi_amg_info; no
+ * reference counterpart. */
+int dfmi_dnn_plan(dfmi_ctx* ctx, int max_layers, int* n_layers, int* kinds);
 
 /* ---- communication accounting per exchange point (multi-rank runs). The reference issues one NCCL group
  * per field and processor patch (dfMatrixOpBase.cu:441-485, dispatch :2402-2491; comm set up at
