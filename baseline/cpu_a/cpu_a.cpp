@@ -94,7 +94,8 @@ struct Level {                       // AMG level: ELL [W][n] + diagonal, work v
 
 struct Ctx {
   int C = 0, Ctot = 0, F = 0, B = 0, P = 0, S = 0, inert = -1;
-  double rdt = 0;
+  double rdt = 0, dt = 0;   // 1 / deltaT (bound to the restatement at every call) and deltaT as given (dfmi_set_delta_t)
+  bool step_courant = false;   // option step.courant: accepted for the callers that set it; the number is always computed on demand
   bool have_sizes = false, have_topo = false, have_geom = false, have_bgeom = false;
   std::vector<int> psize, pkind, cyc_nbr, own, nei, bfc, poff, slot_patch, prim, partner, dims, inert_v;
   std::map<std::string, std::vector<int>> ptype;        // per patch, also registered as "ptype_<f>"
@@ -823,6 +824,28 @@ void time_step(Ctx& x, int n_corr) {
   rho_from_psi(x);
 }
 
+// compressibleCourantNo.H (dfLowMachFoam.C:261): sumPhi = fvc::surfaceSum(mag(phi)) / rho, CoNum = 0.5 max(sumPhi / V)
+// deltaT, meanCoNum = 0.5 (sum(sumPhi) / sum(V)) deltaT. The face loop visits each cell's faces in increasing index
+// (faces are upper-triangular: a cell's neighbour-side faces precede its owned ones), then the boundary slots in slot
+// order -- per cell the GPU gather's order, so sumPhi agrees bitwise and CoNum with it; the two sums run in cell order.
+void courant_no(Ctx& x, double* co, double* mean) {
+  const long C = x.C, F = x.F, B = x.B;
+  const double *phi = x.f("phi"), *bphi = x.f("boundary_phi"), *rho = x.f("rho"), *V = x.work.at("volume").data();
+  const std::vector<int>& pt = x.ptype.at("calculated");
+  std::vector<double> s(C, 0.0);
+  for (long f = 0; f < F; ++f) { const double a = std::fabs(phi[f]); s[x.own[f]] += a; s[x.nei[f]] += a; }
+  for (long b = 0; b < B; ++b) if (x.prim[b] && pt[x.slot_patch[b]] != EMPTY) s[x.bfc[b]] += std::fabs(bphi[b]);
+  double mx = 0.0, sum = 0.0, vol = 0.0;
+  for (long c = 0; c < C; ++c) {
+    const double sp = s[c] / rho[c];
+    mx = std::fmax(mx, sp / V[c]);
+    sum += sp;
+    vol += V[c];
+  }
+  *co = 0.5 * mx * x.dt;
+  *mean = 0.5 * (sum / vol) * x.dt;
+}
+
 void copy_field(Ctx& x, const std::string& name, double* host, long count, int layout, bool to_ctx) {
   auto it = x.fields.find(name);
   CHECK(it != x.fields.end(), "unknown field '" + name + "'");
@@ -865,7 +888,7 @@ int dfmi_set_constant_values(dfmi_ctx* ctx, int num_cells, int num_total_cells, 
     CHECK(num_species >= 2 && num_species <= 64, "num_species must be in [2,64]");
     CHECK(rdelta_t > 0, "rdelta_t must be positive");
     x.C = num_cells; x.Ctot = num_total_cells; x.F = num_surfaces; x.B = num_boundary_surfaces; x.P = num_patches;
-    x.S = num_species; x.rdt = rdelta_t;
+    x.S = num_species; x.rdt = rdelta_t; x.dt = 1.0 / rdelta_t;
     x.psize.assign(patch_size, patch_size + num_patches);
     x.pkind.assign(num_patches, 0);
     x.cyc_nbr.assign(num_patches, -1);
@@ -1072,14 +1095,52 @@ int dfmi_thermo_psip0(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x);
 int dfmi_thermo_correct_psip_rho(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); correct_psip_rho(ctx->x); }); }
 int dfmi_time_step(dfmi_ctx* ctx, int n_corr) { return guard([&] { require_ready(ctx->x); time_step(ctx->x, n_corr); }); }
 int dfmi_sync(dfmi_ctx*) { return 0; }
+// compressibleCourantNo.H / setDeltaT.H (dfLowMachFoam.C:261-262)
+int dfmi_courant_no(dfmi_ctx* ctx, double* co_num, double* mean_co_num) {
+  return guard([&] {
+    CHECK(ctx, "null context");
+    CHECK(co_num && mean_co_num, "dfmi_courant_no: null output pointer");
+    CHECK(ctx->x.have_sizes && ctx->x.have_topo && ctx->x.have_geom && ctx->x.have_bgeom, "mesh not fully initialised");
+    courant_no(ctx->x, co_num, mean_co_num);
+  });
+}
+// every stage reads 1 / deltaT through the restatement's registry, bound again at each call (bind), and the chemistry
+// its interval at each YEqn; the AMG operator values are formed again at every p solve (amg_galerkin): nothing keeps
+// the old step
+int dfmi_set_delta_t(dfmi_ctx* ctx, double delta_t) {
+  return guard([&] {
+    CHECK(ctx, "null context");
+    Ctx& x = ctx->x;
+    CHECK(x.have_sizes, "dfmi_set_delta_t: call dfmi_set_constant_values first");
+    CHECK(delta_t > 0 && delta_t <= 1.79769313486231570e308, "dfmi_set_delta_t: delta_t must be positive and finite");
+    const double rdt = 1.0 / delta_t;
+    CHECK(rdt > 0 && rdt <= 1.79769313486231570e308, "dfmi_set_delta_t: 1 / delta_t is not a positive finite number");
+    x.dt = delta_t;
+    x.rdt = rdt;
+  });
+}
+int dfmi_get_delta_t(dfmi_ctx* ctx, double* delta_t) {
+  return guard([&] {
+    CHECK(ctx && delta_t, "dfmi_get_delta_t: null pointer");
+    CHECK(ctx->x.have_sizes, "dfmi_get_delta_t: call dfmi_set_constant_values first");
+    *delta_t = ctx->x.dt;
+  });
+}
 // no device events on the CPU: the bench times CPU-A with host clocks
 int dfmi_step_timer(dfmi_ctx*, int) { return 0; }
 // CPU-A runs one fixed configuration (the GPU path's defaults: AMG omega 0.9, over-correction 1.4, 6 coarsest sweeps, ...)
-int dfmi_set_option(dfmi_ctx*, const char* key, double) {
-  return guard([&] { throw Error(std::string("dfmi (CPU-A): option '") + key + "' is not configurable here"); });
+// step.courant alone is accepted (dfmi.timestep.advance sets it): dfmi_courant_no computes on demand either way
+int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
+  return guard([&] {
+    if (ctx && key && std::string(key) == "step.courant") { ctx->x.step_courant = value != 0.0; return; }
+    throw Error(std::string("dfmi (CPU-A): option '") + key + "' is not configurable here");
+  });
 }
-int dfmi_get_option(dfmi_ctx*, const char* key, double*) {
-  return guard([&] { throw Error(std::string("dfmi (CPU-A): option '") + key + "' is not configurable here"); });
+int dfmi_get_option(dfmi_ctx* ctx, const char* key, double* value) {
+  return guard([&] {
+    if (ctx && key && value && std::string(key) == "step.courant") { *value = ctx->x.step_courant ? 1.0 : 0.0; return; }
+    throw Error(std::string("dfmi (CPU-A): option '") + key + "' is not configurable here");
+  });
 }
 int dfmi_step_times(dfmi_ctx*, double*, int, int* got) { if (got) *got = 0; return 0; }
 int dfmi_hbm_copy_peak(dfmi_ctx*, double, int, double*) { return guard([&] { throw Error("dfmi (CPU-A): no device memory"); }); }

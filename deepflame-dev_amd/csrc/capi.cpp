@@ -181,6 +181,7 @@ void copy_field(Ctx& x, const std::string& name, const double* host, long count,
 
 void require_ready(Ctx& x) {
   DFMI_CHECK(x.have_sizes && x.have_topo && x.have_geom && x.have_bgeom, "mesh not fully initialised");
+  x.co.fresh = false;   // every entry that may rewrite phi or rho comes through here (dfmi_time_step posts a new record)
   if (!x.ell.ready) build_ell(x);   // gather rows (face lists of the assembly kernels, solver columns)
 }
 
@@ -373,7 +374,8 @@ int dfmi_set_constant_values(dfmi_ctx* ctx, int num_cells, int num_total_cells, 
     DFMI_CHECK(num_species >= 2 && num_species <= 64, "num_species must be in [2,64]");
     DFMI_CHECK(rdelta_t > 0, "rdelta_t must be positive");
     x.C = num_cells; x.Ctot = num_total_cells; x.F = num_surfaces; x.B = num_boundary_surfaces; x.P = num_patches;
-    x.nproc_faces = num_proc_surfaces; x.S = num_species; x.rdt = rdelta_t;
+    x.nproc_faces = num_proc_surfaces; x.S = num_species; x.rdt = rdelta_t; x.dt = 1.0 / rdelta_t;
+    x.co.fresh = false;
     x.psize.assign(patch_size, patch_size + num_patches);
     x.pkind.assign(num_patches, 0);
     x.cyc_nbr.assign(num_patches, -1);
@@ -455,6 +457,8 @@ int dfmi_init_constant_fields_internal(dfmi_ctx* ctx, const double* sf, const do
     x.w.upload(ww, x.stream);
     x.dc.upload(dd, x.stream);
     x.V.upload(volume, x.C, x.stream);
+    x.co.sumV = 0.0;   // gSum(V) of the mean Courant number: constant, summed once, in cell order
+    for (int c = 0; c < x.C; ++c) x.co.sumV += volume[c];
     DFMI_HIP(hipStreamSynchronize(x.stream));
     x.have_md = mesh_distance != nullptr;
     x.have_geom = true;
@@ -654,7 +658,7 @@ int dfmi_thermo_load(dfmi_ctx* ctx, const char* path) {
 }
 
 int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long count, int layout) {
-  return guard([&] { copy_field(ctx->x, name, host, count, layout, true); });
+  return guard([&] { ctx->x.co.fresh = false; copy_field(ctx->x, name, host, count, layout, true); });
 }
 int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, int layout) {
   return guard([&] { copy_field(ctx->x, name, host, count, layout, false); });
@@ -720,8 +724,69 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
     thermo_rho_from_psi(x);         // rho = thermo.rho() (dfLowMachFoam.C:517)
     if (x.chem.mode == 1) chem_check(x);   // the p solves' polls have already passed the chemistry
     if (tsplit) DFMI_HIP(hipStreamWaitEvent(x.stream, x.ev_tr, 0));
+    // compressibleCourantNo.H of the next loop pass, queued now that the step's final phi (last pEqn) and rho are
+    // written: dfmi_courant_no then reads the record instead of launching (option step.courant; off: nothing added)
+    if (x.on("step.courant")) courant_post(x);
     if (x.steptimer.on) x.steptimer.mark(x.stream);
     treset.done = true;
+  });
+}
+
+// compressibleCourantNo.H (dfLowMachFoam.C:261)
+int dfmi_courant_no(dfmi_ctx* ctx, double* co_num, double* mean_co_num) {
+  return guard([&] {
+    DFMI_CHECK(ctx, "null context");
+    Ctx& x = ctx->x;
+    DFMI_CHECK(co_num && mean_co_num, "dfmi_courant_no: null output pointer");
+    if (!x.co.fresh) {   // no record of the fields as they stand (step.courant off, or something was set since)
+      require_ready(x);
+      courant_post(x);
+    }
+    // wait (spinning) for the record queued last, as the solvers' Poller does: no stream drain. A stream that drained
+    // without posting it (a failed launch) is an error rather than a hang.
+    const CoRec* r = x.co.h;
+    const long long seq = x.co.seq;
+    for (long spins = 0; __atomic_load_n(&r->seq, __ATOMIC_ACQUIRE) < seq; ++spins) {
+      if ((spins & 0xfff) != 0xfff) continue;
+      const hipError_t q = hipStreamQuery(x.stream);
+      if (q != hipErrorNotReady && __atomic_load_n(&r->seq, __ATOMIC_ACQUIRE) < seq) {
+        x.co.fresh = false;
+        DFMI_HIP(q);
+        throw Error("dfmi_courant_no: the stream drained without posting the Courant-number record");
+      }
+    }
+    *co_num = r->co;
+    *mean_co_num = r->mean;
+  });
+}
+
+// setDeltaT.H (dfLowMachFoam.C:262). Every kernel takes 1 / deltaT by value at its launch (Ctx::view, MeshView::rdt:
+// ddt terms, ddtCorr, dpdt, the waveTransmissive valueFraction) and the chemistry its interval (do_Y_front), so nothing
+// on the device keeps the old step; the chemistry's remembered sub-step (chem_stats row 2) is capped by the interval
+// where it is read (chem.hip: h = min(dt, remembered)). What does outlive a step is the pressure AMG's operators.
+int dfmi_set_delta_t(dfmi_ctx* ctx, double delta_t) {
+  return guard([&] {
+    DFMI_CHECK(ctx, "null context");
+    Ctx& x = ctx->x;
+    DFMI_CHECK(x.have_sizes, "dfmi_set_delta_t: call dfmi_set_constant_values first");
+    DFMI_CHECK(delta_t > 0 && delta_t <= 1.79769313486231570e308, "dfmi_set_delta_t: delta_t must be positive and finite");
+    const double rdt = 1.0 / delta_t;
+    DFMI_CHECK(rdt > 0 && rdt <= 1.79769313486231570e308, "dfmi_set_delta_t: 1 / delta_t is not a positive finite number");
+    if (delta_t != x.dt) {   // a posted Courant number was formed with the old step
+      x.dt = delta_t;
+      x.co.fresh = false;
+    }
+    if (rdt == x.rdt) return;   // the step the kernels run with already: nothing changes, nothing is reset
+    x.rdt = rdt;
+    x.amg.age = 0;   // ends the cross-step reuse window (amg.reuse_steps): the next first corrector rebuilds
+  });
+}
+
+int dfmi_get_delta_t(dfmi_ctx* ctx, double* delta_t) {
+  return guard([&] {
+    DFMI_CHECK(ctx && delta_t, "dfmi_get_delta_t: null pointer");
+    DFMI_CHECK(ctx->x.have_sizes, "dfmi_get_delta_t: call dfmi_set_constant_values first");
+    *delta_t = ctx->x.dt;
   });
 }
 

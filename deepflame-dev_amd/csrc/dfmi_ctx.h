@@ -277,10 +277,34 @@ inline const OptDef* option_defs(int& n) {
                                       // (13.89 -> 13.92 ms per step, 3 rounds each in one call, round 6: not the default)
     {"halo.overlap", 0},              // several ranks: solver halo exchanges on a comm stream while the interior rows run
                                       // (read per solve; DFMI_HALO_OVERLAP sets the default when the communicator is set)
+    {"step.courant", 0},              // 1: dfmi_time_step ends with the Courant-number kernel and posts its record for
+                                      // dfmi_courant_no (compressibleCourantNo.H, dfLowMachFoam.C:261); 0: nothing added
   };
   n = (int)(sizeof(d) / sizeof(d[0]));
   return d;
 }
+
+// Courant number (fv_kernels.hip courant_post; dfmi_courant_no): the record the last kernel of the reduction stores
+// into host-coherent pinned memory, `seq` last (system-scope release), as the solvers' PollRec
+struct CoRec { double co, mean; long long seq; };
+struct Courant {
+  CoRec* h = nullptr;
+  CoRec* d = nullptr;
+  long long seq = 0;          // records queued so far
+  bool fresh = false;         // the last queued record describes the fields and the step size as they stand
+  double sumV = 0;            // sum of this rank's cell volumes, in cell order (constant: summed once at setup)
+  DevBuf<double> partial, tri, all;   // per-block (sum, max); this rank's (max, sum, volume); every rank's
+  Courant() = default;
+  Courant(const Courant&) = delete;
+  Courant& operator=(const Courant&) = delete;
+  ~Courant() { if (h) (void)hipHostFree(h); }
+  void ensure() {
+    if (h) return;
+    DFMI_HIP(hipHostMalloc((void**)&h, sizeof(CoRec), hipHostMallocCoherent | hipHostMallocMapped));
+    h->co = 0; h->mean = 0; h->seq = 0;
+    DFMI_HIP(hipHostGetDevicePointer((void**)&d, h, 0));
+  }
+};
 
 struct Ctx {
   int device = 0;
@@ -300,7 +324,10 @@ struct Ctx {
   int Fs = 0;                    // face storage size (owner-slot layout: kmax * C; otherwise F)
   bool fslot = false;
   std::vector<int> h_fst;        // OpenFOAM face -> storage index
-  double rdt = 0;
+  double rdt = 0;                // 1 / deltaT: what every kernel reads (MeshView::rdt, by value at each launch)
+  double dt = 0;                 // deltaT as the caller gave it (dfmi_set_delta_t; 1 / rdelta_t at setup): dfmi_get_delta_t
+                                 // and the Courant number
+  Courant co;
   int inert = -1;
   bool have_sizes = false, have_topo = false, have_geom = false, have_bgeom = false;
   bool have_md = false;           // mesh_distance was given (the limited schemes' d; zeros otherwise)
@@ -507,6 +534,7 @@ void e_assemble_back(Ctx& x);    // boundary energy gradient, he's boundary valu
 void e_post_solve(Ctx& x);
 void conv_weights(Ctx& x);   // div(phi,Yi_h) weights (start of YEqn; EEqn reuses them)
 void copy_old(Ctx& x);
+void courant_post(Ctx& x);   // queues the Courant-number reduction and its record (Ctx::co), no synchronisation
 void zero_d_step(Ctx& x, double dt);   // df0DFoam loop body for every cell
 void thermo_rho_from_psi(Ctx& x);
 void thermo_psip0(Ctx& x);

@@ -646,6 +646,78 @@ __global__ void k_rho(MeshView m, const int8_t* __restrict__ ty, const double* _
   if (odiag) { odiag[c] = diag; osrc[c] = src; }
 }
 
+// ------------------------------------------------------------------ Courant number
+// compressibleCourantNo.H of OpenFOAM-7 (dfLowMachFoam.C:261): sumPhi = fvc::surfaceSum(mag(phi)) / rho,
+// CoNum = 0.5 gMax(sumPhi / V) deltaT, meanCoNum = 0.5 (gSum(sumPhi) / gSum(V)) deltaT. One thread per cell sums
+// |phi| over the cell's faces in the project's face order (every internal face for its owner and its neighbour, then
+// the cell's primary boundary slots: a processor face adds this rank's flux only), divides by rho, and the block leaves
+// (sum of sumPhi, max of sumPhi / V) at its LOGICAL block index (xcd_block), so the second stage adds the partials in
+// cell order whatever the dispatch order. HBM-bound: per cell |phi| of its owned faces and, from the L2, of its
+// neighbour-side faces, rho, V and the boundary-slot range. Threads past the last cell contribute the neutral 0 (every
+// term is >= 0) and stay in the reduction: wave_sum needs the whole wave.
+__device__ __forceinline__ double wave_max(double v) {
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+template <int WT>
+__global__ void __launch_bounds__(TPB) k_courant(MeshView m, const int8_t* __restrict__ ty, const double* __restrict__ phi,
+                                                 const double* __restrict__ bphi, const double* __restrict__ rho,
+                                                 double* __restrict__ partial) {
+  __shared__ double sh[TPB / 64][2];
+  const int lb = xcd_block();
+  const int t = lb * blockDim.x + threadIdx.x;
+  double sp = 0.0, ra = 0.0;
+  if (t < m.C) {
+    const int c = cell_of(m, t);
+    double s = 0.0;
+    each_face<WT>(m, c, [&](int f, int, bool) { s += fabs(phi[f]); });
+    each_slot(m, ty, c, [&](int b, int) { s += fabs(bphi[b]); });
+    sp = s / rho[c];
+    ra = sp / m.V[c];
+  }
+  const double ws = wave_sum(sp), wm = wave_max(ra);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) { sh[wid][0] = ws; sh[wid][1] = wm; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0, mx = 0.0;
+#pragma unroll
+    for (int w = 0; w < TPB / 64; ++w) { a += sh[w][0]; mx = fmax(mx, sh[w][1]); }
+    partial[2 * lb] = a;
+    partial[2 * lb + 1] = mx;
+  }
+}
+// the gathered per-rank (max, sum, volume) combined in rank order and posted to host-coherent pinned memory: plain
+// stores, then `seq` with a system-scope release (the host spins on it, as on the solvers' PollRec)
+__device__ __forceinline__ void courant_record(const double* __restrict__ tri, int nranks, double dt, CoRec* rec, long long seq) {
+  double mx = 0.0, s = 0.0, v = 0.0;
+  for (int r = 0; r < nranks; ++r) { mx = fmax(mx, tri[3 * r]); s += tri[3 * r + 1]; v += tri[3 * r + 2]; }
+  rec->co = 0.5 * mx * dt;
+  rec->mean = 0.5 * (s / v) * dt;
+  __hip_atomic_store(&rec->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// second stage, one block: the per-block partials in a fixed order (thread i takes partials i, i + 256, ...; any
+// count) -> this rank's (max, sum, volume); one rank: the record too
+__global__ void __launch_bounds__(TPB) k_courant_reduce(const double* __restrict__ partial, int nblk, double sumV,
+                                                        double* __restrict__ tri, CoRec* rec, double dt, long long seq) {
+  __shared__ double sh[TPB / 64][2];
+  double s = 0.0, mx = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += TPB) { s += partial[2 * i]; mx = fmax(mx, partial[2 * i + 1]); }
+  const double ws = wave_sum(s), wm = wave_max(mx);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) { sh[wid][0] = ws; sh[wid][1] = wm; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double t3[3] = {0.0, 0.0, sumV};
+#pragma unroll
+  for (int w = 0; w < TPB / 64; ++w) { t3[1] += sh[w][0]; t3[0] = fmax(t3[0], sh[w][1]); }
+  tri[0] = t3[0]; tri[1] = t3[1]; tri[2] = t3[2];
+  if (rec) courant_record(t3, 1, dt, rec, seq);
+}
+__global__ void k_courant_combine(const double* __restrict__ all, int nranks, double dt, CoRec* rec, long long seq) {
+  if (threadIdx.x == 0) courant_record(all, nranks, dt, rec, seq);
+}
+
 // ------------------------------------------------------------------ UEqn
 // gradU (fvc_grad_vector :944-1107) -> T = mu*dev2(T(gradU)) (scale_dev2t_tensor_kernel :623) for
 // cells, and for the cell's non-coupled slots the corrected boundary gradient (:1239-1327) -> bT.
@@ -2038,6 +2110,31 @@ void rho_process(Ctx& x, bool write_matrix) {
   LAUNCH_W(k_rho, x.C, x.view(), x.st("rho"), x.f("rho_old"), x.f("phi"), x.f("boundary_phi"), x.f("rho"), od, os);
   k_bc_correct(x, "rho", x.f("rho"), x.f("boundary_rho"), 1);
   halo_fields(x, {"rho"});
+}
+
+// compressibleCourantNo.H: the per-cell gather, the fixed-order second stage and the record, queued on the context
+// stream with no synchronisation (dfmi_courant_no waits on the record; dfmi_time_step with step.courant ends with this).
+// Several ranks: the per-rank triples are all-gathered and combined in rank order, every rank to the same bits.
+void courant_post(Ctx& x) {
+  Courant& co = x.co;
+  co.ensure();
+  const int nblk = blocks_for(x.C, TPB);
+  if (co.partial.n < (size_t)2 * nblk) co.partial.alloc((size_t)2 * nblk);
+  if (co.tri.n == 0) co.tri.alloc(3);
+  LAUNCH_W(k_courant, x.C, x.view(), x.st("calculated"), x.f("phi"), x.f("boundary_phi"), x.f("rho"), co.partial.p);
+  const long long seq = ++co.seq;
+  const bool multi = x.nranks > 1;
+  hipLaunchKernelGGL(k_courant_reduce, dim3(1), dim3(TPB), 0, x.stream, co.partial.p, nblk, co.sumV, co.tri.p,
+                     multi ? nullptr : co.d, x.dt, seq);
+  DFMI_HIP(hipGetLastError());
+  if (multi) {
+    CommTag _ct(x, "courant");
+    if (co.all.n < (size_t)3 * x.nranks) co.all.alloc((size_t)3 * x.nranks);
+    halo_allgather(x, co.tri.p, co.all.p, 3);
+    hipLaunchKernelGGL(k_courant_combine, dim3(1), dim3(64), 0, x.stream, co.all.p, x.nranks, x.dt, co.d, seq);
+    DFMI_HIP(hipGetLastError());
+  }
+  co.fresh = true;
 }
 
 // ---- schemes (dfmi_set_scheme): buffers allocated on first use

@@ -59,6 +59,7 @@ SIGNATURES = {
     "dfmi_thermo_update_rho": [_P], "dfmi_thermo_psip0": [_P], "dfmi_thermo_correct_psip_rho": [_P],
     "dfmi_U_get_HbyA": [_P], "dfmi_p_process": [_P], "dfmi_post_time_step": [_P],
     "dfmi_time_step": [_P, C.c_int], "dfmi_sync": [_P],
+    "dfmi_courant_no": [_P, _DP, _DP], "dfmi_set_delta_t": [_P, C.c_double], "dfmi_get_delta_t": [_P, _DP],
     "dfmi_step_timer": [_P, C.c_int], "dfmi_step_times": [_P, _DP, C.c_int, _IP],
     "dfmi_hbm_copy_peak": [_P, C.c_double, C.c_int, _DP],
     "dfmi_assemble": [_P, C.c_char_p],
@@ -435,6 +436,24 @@ class Context:
 
     def time_step(self, n_corr=2):
         self._call("dfmi_time_step", self.h, int(n_corr))
+
+    def courant_no(self):
+        """(CoNum, meanCoNum) of the current phi, rho and step size (include/dfmi.h dfmi_courant_no:
+        compressibleCourantNo.H, dfLowMachFoam.C:261). Several ranks: a collective."""
+        co = C.c_double(); mean = C.c_double()
+        self._call("dfmi_courant_no", self.h, C.byref(co), C.byref(mean))
+        return co.value, mean.value
+
+    def set_delta_t(self, dt: float):
+        """the step size of every later call (include/dfmi.h dfmi_set_delta_t: setDeltaT.H, dfLowMachFoam.C:262;
+        the rule that picks it is dfmi.timestep.next_delta_t)"""
+        self._call("dfmi_set_delta_t", self.h, float(dt))
+
+    def delta_t(self) -> float:
+        """the step size in force (include/dfmi.h dfmi_get_delta_t)"""
+        v = C.c_double()
+        self._call("dfmi_get_delta_t", self.h, C.byref(v))
+        return v.value
 
     def comm_timer(self, on: bool = True):
         """reset and arm (or disarm) the per-exchange-point communication accounting"""

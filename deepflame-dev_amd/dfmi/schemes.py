@@ -63,17 +63,32 @@ def scheme_codes(schemes: dict) -> tuple[list, list]:
     return codes, ks
 
 
+def dict_entries(txt: str) -> list:
+    """the `keyword value...;` entries of a piece of OpenFOAM dictionary text in file order, as
+    (keyword, value) pairs; // and /* */ comments are dropped, and so is every { } block with its name
+    (FoamFile, sub-dictionaries): the entries of one level only"""
+    import re
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"//.*", "", txt)
+    while True:
+        flat = re.sub(r"[^\s;{}]+\s*\{[^{}]*\}", "", txt)
+        if flat == txt:
+            break
+        txt = flat
+    out = []
+    for line in txt.split(";"):
+        tok = line.split()
+        if len(tok) >= 2:
+            out.append((tok[0], " ".join(tok[1:])))
+    return out
+
+
 def read_fv_schemes(path: str) -> dict:
     """the divSchemes entries of a case's system/fvSchemes for TERMS ({term: scheme})"""
     import re
     txt = open(path).read()
     txt = re.sub(r"//.*", "", txt)
     mo = re.search(r"divSchemes\s*\{(.*?)\}", txt, re.S)
-    out = {}
     if not mo:
-        return out
-    for line in mo.group(1).split(";"):
-        tok = line.split()
-        if len(tok) >= 2 and tok[0] in TERMS:
-            out[tok[0]] = " ".join(tok[1:])
-    return out
+        return {}
+    return {k: v for k, v in dict_entries(mo.group(1)) if k in TERMS}

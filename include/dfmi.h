@@ -165,6 +165,36 @@ int dfmi_post_time_step(dfmi_ctx* ctx);         /* dfMatrixDataBase::postTimeSte
 /* the whole loop body above with n_corr pressure correctors */
 int dfmi_time_step(dfmi_ctx* ctx, int n_corr);   /* non-zero also when chemistry hit its step limit */
 int dfmi_sync(dfmi_ctx* ctx);
+
+/* ---- adjustable time step: the first two lines of the time loop, dfLowMachFoam.C:261-262
+ * (#include "compressibleCourantNo.H", #include "setDeltaT.H"). The reference GPU path has no counterpart: its
+ * step is fixed at setup (createGPUSolver.H:152 "TODO: get deltaT from time API"). */
+/* compressibleCourantNo.H (dfLowMachFoam.C:261) on the device, from phi, boundary_phi, rho and the cell volumes as
+ * they stand, with the step size in force:
+ *   sumPhi_c  = (sum over the faces f of cell c of |phi_f|) / rho_c        fvc::surfaceSum(mag(phi)) / rho
+ *   CoNum     = 0.5 max_c(sumPhi_c / V_c) deltaT                           (gMax over ranks)
+ *   meanCoNum = 0.5 (sum_c sumPhi_c / sum_c V_c) deltaT                    (gSum over ranks)
+ * Every internal face counts for its owner and its neighbour, every boundary face of every patch kind for its
+ * face cell (a processor face with this rank's flux only). Per-block partials reduced in a fixed order, no
+ * floating-point atomics; with several ranks the per-rank (max, sum, volume) are all-gathered and combined in rank
+ * order, so every rank returns the same bits (a collective: every rank calls it at the same point). Synchronises on
+ * the result only. Right after a dfmi_time_step run with the option step.courant = 1 it returns the record that
+ * step left in pinned memory, without a launch. */
+int dfmi_courant_no(dfmi_ctx* ctx, double* co_num, double* mean_co_num);
+/* setDeltaT.H (dfLowMachFoam.C:262): the step size of every later dfmi_pre_time_step / dfmi_time_step /
+ * per-equation call -- ddt terms, ddtCorr, dpdt, the waveTransmissive valueFraction 1 / (1 + w deltaT deltaCoeffs)
+ * and the chemistry's integration interval; the chemistry's remembered sub-step is capped by the new interval.
+ * RR of the DF-ODENet surrogate is a rate formed with dt_infer and does not depend on deltaT, as in the reference
+ * (dfChemistrySolver.cu:191). A changed step ends the cross-step reuse of the pressure AMG operators (option
+ * amg.reuse_steps): the p operator scales with deltaT through rAU, and the next first corrector rebuilds the
+ * hierarchy values as the reference does at every solve (AmgXSolver.cu:268-281). The step-size rule itself
+ * (maxCo, maxDeltaT) stays with the caller, as in OpenFOAM. Errors: delta_t not positive or not finite; a call
+ * before dfmi_set_constant_values. Setting the value in force changes and resets nothing. dfmi_zero_d_step keeps
+ * its own dt argument. */
+int dfmi_set_delta_t(dfmi_ctx* ctx, double delta_t);
+/* the step size in force: the last dfmi_set_delta_t value, or 1 / rdelta_t of dfmi_set_constant_values */
+int dfmi_get_delta_t(dfmi_ctx* ctx, double* delta_t);
+
 /* per-step HIP events on the context stream (bench: median step time); no reference counterpart (its
  * TIME_GPU host ticks, dfLowMachFoam.C:249-531). dfmi_step_times returns got = steps timed since arming */
 int dfmi_step_timer(dfmi_ctx* ctx, int on);
@@ -200,7 +230,8 @@ int dfmi_set_preconditioner(dfmi_ctx* ctx, const char* eqn, const char* name);
  * refused, and so is 1 together with global_coarse),
  * "solver.*" (even_odd, small, row_classes), "pcg.*" (face_form, fuse_l0), "fv.*" (hex_walk, csr_walk,
  * species_generic, yprep_brick), "chem.*" (method 0 ROS3 | 1 extrapolation, generated, binning),
- * "dnn.tuned_gemm"; keys and
+ * "dnn.tuned_gemm", "step.courant" (1: dfmi_time_step queues the Courant-number kernel behind its last
+ * kernel and posts the result to pinned memory for dfmi_courant_no; 0, the default: nothing added); keys and
  * defaults in INTEGRATION.md. Solver-structure keys must be set before the first solve; unknown keys fail. */
 int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value);
 int dfmi_get_option(dfmi_ctx* ctx, const char* key, double* value);
