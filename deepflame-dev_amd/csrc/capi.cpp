@@ -247,7 +247,7 @@ bool step_overlap(const Ctx& x) {
 void do_U_Y_fork(Ctx& x) {
   if (!x.stream2) {
     DFMI_HIP(hipStreamCreateWithFlags(&x.stream2, hipStreamNonBlocking));
-    for (hipEvent_t* e : {&x.ev_fork, &x.ev_join, &x.ev_u, &x.ev_e, &x.ev_cw, &x.ev_th, &x.ev_tr})
+    for (hipEvent_t* e : {&x.ev_fork, &x.ev_join, &x.ev_u, &x.ev_e, &x.ev_cw})
       DFMI_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
   }
   DFMI_HIP(hipEventRecord(x.ev_fork, x.stream));
@@ -262,13 +262,6 @@ void do_U_Y_fork(Ctx& x) {
   OnStream _os(x, x.stream2);
   do_Y_front(x, false, x.ev_cw);
   DFMI_HIP(hipEventRecord(x.ev_join, x.stream2));
-}
-void do_U_Y(Ctx& x) {
-  if (!step_overlap(x)) { do_U(x); do_Y(x); return; }
-  do_U_Y_fork(x);
-  do_U(x);
-  DFMI_HIP(hipStreamWaitEvent(x.stream, x.ev_join, 0));
-  do_Y_back(x);
 }
 void do_E_back(Ctx& x) {
   Matrix& A = x.mE;
@@ -285,7 +278,7 @@ void do_E(Ctx& x) {
 // so they run on the side stream after both while the main stream solves the species; the rest of the
 // assembly needs the solved Y (the thermo's boundary energy gradient) and follows the Y solve
 void do_U_Y_E(Ctx& x) {
-  if (!step_overlap(x)) { do_U_Y(x); do_E(x); return; }
+  if (!step_overlap(x)) { do_U(x); do_Y(x); do_E(x); return; }
   do_U_Y_fork(x);
   do_U(x);
   DFMI_HIP(hipEventRecord(x.ev_u, x.stream));
@@ -300,25 +293,6 @@ void do_U_Y_E(Ctx& x) {
   DFMI_HIP(hipStreamWaitEvent(x.stream, x.ev_e, 0));
   e_assemble_back(x);
   do_E_back(x);
-}
-// correctThermo split in two: the state the pressure corrector reads (T, he, psi, rho) on the main stream, and the
-// transport (mu, alpha, rhoD, hai) -- read by nothing before the next time step's equations -- on the side stream,
-// where it runs beside the p solves (their coarse AMG levels leave most CUs idle). Its inputs (T, Y) are not
-// written again in the step; the main stream waits for it at the end of the step. Option thermo.split (0: fused).
-bool do_thermo_split(Ctx& x) {
-  if (!step_overlap(x) || !x.on("thermo.split") || species_generic(x) || !x.stream2) {
-    thermo_correct(x, false);
-    return false;
-  }
-  thermo_correct(x, false, 1);
-  DFMI_HIP(hipEventRecord(x.ev_th, x.stream));
-  {
-    OnStream _os(x, x.stream2);
-    DFMI_HIP(hipStreamWaitEvent(x.stream2, x.ev_th, 0));
-    thermo_correct(x, false, 2);
-    DFMI_HIP(hipEventRecord(x.ev_tr, x.stream2));
-  }
-  return true;
 }
 void do_p(Ctx& x) {
   p_assemble(x);
@@ -703,7 +677,7 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
     rho_process(x, false);          // rhoEqn (first PIMPLE iteration)
     do_U_Y_E(x);                    // UEqn, YEqn, EEqn (one rank: the chemistry and YEqn assembly beside the
                                     // UEqn, the EEqn assembly beside the Y solve)
-    const bool tsplit = do_thermo_split(x);   // correctThermo (the transport half beside the p solves)
+    thermo_correct(x, false);       // correctThermo
     for (int i = 0; i < n_corr; ++i) {   // pEqn_GPU.H
       // rho = psi p: the first corrector's is what correctThermo just wrote (the same product of the same p and psi,
       // halo included); psip0 = psi p feeds only correctPsipRho, skipped below (the field is not updated here)
@@ -723,7 +697,6 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
     }
     thermo_rho_from_psi(x);         // rho = thermo.rho() (dfLowMachFoam.C:517)
     if (x.chem.mode == 1) chem_check(x);   // the p solves' polls have already passed the chemistry
-    if (tsplit) DFMI_HIP(hipStreamWaitEvent(x.stream, x.ev_tr, 0));
     // compressibleCourantNo.H of the next loop pass, queued now that the step's final phi (last pEqn) and rho are
     // written: dfmi_courant_no then reads the record instead of launching (option step.courant; off: nothing added)
     if (x.on("step.courant")) courant_post(x);

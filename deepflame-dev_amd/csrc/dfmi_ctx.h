@@ -26,7 +26,7 @@
 
 namespace dfmi {
 
-constexpr int SCODE_PAD = -1;   // row-class source code of a padding entry (esrc PAD)
+constexpr int SCODE_PAD = -1;   // row-class source code of a padding entry (esrc PAD; build_ell's class key)
 
 struct MeshView {
   int C, F, B, S;
@@ -34,12 +34,11 @@ struct MeshView {
   int fslot;                // face storage in owner-slot order (k*C + c) rather than OpenFOAM order
   const int8_t* sprim;   // 1 = primary slot (owner side), 0 = processor [internal n] slot
   const double *Sf, *magSf, *w, *dc, *V, *bSf, *bmagSf, *bw, *bdc;
-  const int *ecol, *esrc;   // solver gather rows [W][C] (linsolve.hip build_ell): the face loops read them
+  // solver gather rows [W][C] (linsolve.hip build_ell): the face loops read them. Entry k of cell c's row is
+  // column ecol[k C + c] and coefficient source esrc[k C + c] (2 f + own for the face at storage f, -(b + 1)
+  // for boundary slot b, INT_MIN padding)
+  const int *ecol, *esrc;
   int W;
-  // row classes (ColView): column offsets and source codes per class [ncls][W]; a source code is
-  // 2 kslot + own (face storage kslot * C + owner cell), SCODE_PAD for padding, CEXPL: read esrc
-  const uint8_t* ecls;
-  const int *ectab, *estab;
   double rdt;
   // hex box in blockMesh order (cell c = i + nx (j + ny k), internal faces towards +x/+y/+z in owner-slot
   // storage, build_ell checked every row against it): the face walk computes face and neighbour indices
@@ -52,23 +51,6 @@ struct MeshView {
   // BiCGStab rows (k_ell_build for U/E, k_y_assemble_ell) read it.
   const int* eopos;
 };
-
-// entry k of cell c's gather row: column j and coefficient source e (2 f + own for the face at storage f,
-// -(b + 1) for boundary slot b, INT_MIN padding), from the row class cl (ecls_of) or the explicit arrays
-__device__ __forceinline__ int ecls_of(const MeshView& m, int c) { return m.ecls ? (int)m.ecls[c] : -1; }
-__device__ __forceinline__ void erow(const MeshView& m, int cl, int k, int c, int& j, int& e) {
-  const long C = m.C;
-  if (cl >= 0) {
-    const int o = m.ectab[cl * m.W + k], sc = m.estab[cl * m.W + k];
-    j = o != CEXPL ? c + o : m.ecol[k * C + c];
-    if (sc == SCODE_PAD) e = CEXPL;   // == INT_MIN, the ELL padding code
-    else if (sc != CEXPL) e = 2 * ((sc >> 1) * (int)C + ((sc & 1) ? c : j)) + (sc & 1);
-    else e = m.esrc[k * C + c];
-    return;
-  }
-  j = m.ecol[k * C + c];
-  e = m.esrc[k * C + c];
-}
 
 // interpolation / convection schemes of the terms the reference GPU path hard-wires (dfmi_set_scheme;
 // dfmi/schemes.py): div(phi,Yi_h), div(phi,K), div(hDiffCorrFlux)
@@ -273,8 +255,6 @@ inline const OptDef* option_defs(int& n) {
     {"chem.generated", 1},            // compiled-in kinetics when the mechanism's fingerprint matches
     {"chem.binning", 2},              // cells launched in cost-binned order: 1 over the mesh, 2 inside 4096-cell tiles
     {"dnn.tuned_gemm", 1},            // DF-ODENet layers by the shape-tuned kernels (0: k_mlp_gemm for every layer)
-    {"thermo.split", 0},              // time step: the transport half of correctThermo on the side stream beside the p solve
-                                      // (13.89 -> 13.92 ms per step, 3 rounds each in one call, round 6: not the default)
     {"halo.overlap", 0},              // several ranks: solver halo exchanges on a comm stream while the interior rows run
                                       // (read per solve; DFMI_HALO_OVERLAP sets the default when the communicator is set)
     {"step.courant", 0},              // 1: dfmi_time_step ends with the Courant-number kernel and posts its record for
@@ -369,9 +349,9 @@ struct Ctx {
     DevBuf<int> brow;            // those rows, ascending
     int nb = 0;
     // row classes (ColView; built when the mesh has <= 255 distinct rows and owner-slot face storage;
-    // DFMI_ROW_CLASSES=0: explicit columns everywhere)
+    // option solver.row_classes = 0: explicit columns everywhere)
     DevBuf<uint8_t> cls;
-    DevBuf<int> ctab, stab;
+    DevBuf<int> ctab;
     DevBuf<int> csStart, csSlot, scol;   // coupled slots per cell and their columns (FaceOp)
     int ncls = 0;
     ColView cols() const {
@@ -412,8 +392,7 @@ struct Ctx {
   SolverWs& sws() { return ws_is_y ? ws_y : ws; }
   // side stream of the time step (dfmi_time_step: chemistry + YEqn preparation beside the UEqn) and its events
   hipStream_t stream2 = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_u = nullptr, ev_e = nullptr, ev_cw = nullptr, ev_th = nullptr,
-            ev_tr = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_u = nullptr, ev_e = nullptr, ev_cw = nullptr;
   // final solver state of the last solve of each equation, copied asynchronously at the end of the
   // solve; dfmi_solver_stats synchronises and reads it (no host sync inside a time step)
   struct StatSnap { PinnedBuf<double> h; int nsys = 0; };
@@ -435,10 +414,6 @@ struct Ctx {
     m.cbStart = cbStart; m.cbSlot = cbSlot; m.bfc = bfc; m.partner = partner; m.sprim = sprim;
     m.Sf = Sf; m.magSf = magSf; m.w = w; m.dc = dc; m.V = V; m.bSf = bSf; m.bmagSf = bmagSf; m.bw = bw; m.bdc = bdc;
     m.ecol = ell.col; m.esrc = ell.src; m.W = ell.ready ? ell.W : 0;
-    // the assembly face loops and the ELL fold read explicit rows (class lookups through the global table
-    // measured slower for these latency-bound gathers, round 3)
-    m.ecls = nullptr;
-    m.ectab = ell.ctab.p; m.estab = ell.stab.p;
     m.rdt = rdt;
     m.trav = trav.n ? trav.p : nullptr;
     m.hx = hex[0]; m.hy = hex[1]; m.hz = hex[2];
@@ -542,9 +517,7 @@ void thermo_correct_psip_rho(Ctx& x);
 // thermo.hip
 void thermo_upload(Ctx& x);
 std::vector<double> heat_of_formation_per_mass(int S, const double* W, const double* nasa);   // hc_i (Qdot weights)
-// part 0: the whole update; 1: the state (T, he, psi, rho); 2: the transport (mu, alpha, rhoD, hai) at the
-// current T -- the time step runs part 2 on the side stream beside the pressure corrector
-void thermo_correct(Ctx& x, bool from_T, int part = 0);
+void thermo_correct(Ctx& x, bool from_T);
 // boundary_heGradient on gradientEnergy slots of he (0 elsewhere)
 void thermo_energy_gradient(Ctx& x);
 // linsolve.hip

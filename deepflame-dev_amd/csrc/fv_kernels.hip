@@ -108,9 +108,9 @@ template <int WT, class FN> __device__ __forceinline__ void each_face(const Mesh
     if (k < m.hz - 1) fn((hxp + hyp) * C + c, c + nxy, true);
   } else if constexpr (WT > 0) {
     int es[WT], cs[WT];
-    const int cl = ecls_of(m, c);
+    const long C = m.C;
 #pragma unroll
-    for (int k = 0; k < WT; ++k) erow(m, cl, k, c, cs[k], es[k]);
+    for (int k = 0; k < WT; ++k) { cs[k] = m.ecol[k * C + c]; es[k] = m.esrc[k * C + c]; }
 #pragma unroll
     for (int k = 0; k < WT; ++k)
       if (es[k] >= 0) fn(es[k] >> 1, cs[k], (es[k] & 1) != 0);   // slots (< 0) and padding skipped
@@ -1474,9 +1474,6 @@ __global__ void __launch_bounds__(TPB) k_y_assemble(MeshView m, const int8_t* __
 // faces, coupled slots), dS = diag + sum internalCoeffs and rhs = source + non-coupled
 // boundaryCoeffs in slot order -- bitwise what k_ell_build makes from the LDU arrays, without writing
 // and re-reading lower/upper/internalCoeffs/boundaryCoeffs.
-// (the species in two groups, each group its own walk over the cell's faces and slots, bitwise the same: 94 VGPRs and
-// no spill under the side-stream cap, but 660 against 590-610 us per launch and 13.88-13.94 against 13.70-13.76 ms
-// per step, round 6 -- not kept)
 template <int S, int WT>
 __global__ void __launch_bounds__(TPB) DFMI_WAVES(5) k_y_assemble_ell(MeshView m, const int8_t* __restrict__ tyY, int inert,
     const double* __restrict__ Y, const double* __restrict__ bY, const double* __restrict__ rhoD,
@@ -1489,78 +1486,66 @@ __global__ void __launch_bounds__(TPB) DFMI_WAVES(5) k_y_assemble_ell(MeshView m
   if (c >= m.C) return;
   const int pc = m.eopos ? m.eopos[c] : c;   // the solver row of c (even-odd layout)
   const long C = m.C, B = m.B;
-  auto group = [&](const int g0) {
-    constexpr int G = S;
-    double d1 = 0.0, d2 = 0.0;
-    double dL[G], rc[G];
+  double d1 = 0.0, d2 = 0.0;
+  double dL[S], rc[S];
 #pragma unroll
-    for (int j = 0; j < G; ++j) { const int s = g0 + j; dL[j] = 0.0; rc[j] = s < S ? rhoD[s * C + c] : 0.0; }
-    int k = 0;
-    each_face<WT>(m, c, [&](int f, int o2, bool own) {
-      const double ph = phi[f], pu = phiUc[f];
-      const double wu = wY ? wY[f] : (ph >= 0 ? 1.0 : 0.0);
-      const double L1 = -wu * ph, U1 = L1 + ph;
-      const double L2 = -wu * pu, U2 = L2 + pu;
-      if (own) { d1 -= L1; d2 -= L2; } else { d1 -= U1; d2 -= U2; }
-      const double w = m.w[f], dcf = m.dc[f], ms = m.magSf[f];
-      const double Ls = L1 + L2, Us = U1 + U2;
+  for (int s = 0; s < S; ++s) { dL[s] = 0.0; rc[s] = rhoD[s * C + c]; }
+  int k = 0;
+  each_face<WT>(m, c, [&](int f, int o2, bool own) {
+    const double ph = phi[f], pu = phiUc[f];
+    const double wu = wY ? wY[f] : (ph >= 0 ? 1.0 : 0.0);
+    const double L1 = -wu * ph, U1 = L1 + ph;
+    const double L2 = -wu * pu, U2 = L2 + pu;
+    if (own) { d1 -= L1; d2 -= L2; } else { d1 -= U1; d2 -= U2; }
+    const double w = m.w[f], dcf = m.dc[f], ms = m.magSf[f];
+    const double Ls = L1 + L2, Us = U1 + U2;
 #pragma unroll
-      for (int j = 0; j < G; ++j) {
-        const int s = g0 + j;
-        if (s >= S) break;
-        if (s == inert) continue;
-        const int ss = s < inert ? s : s - 1;
-        const double rn = rhoD[s * C + o2];
-        const double UL = dcf * ((own ? interp_f(w, rc[j], rn) : interp_f(w, rn, rc[j])) * ms);
-        dL[j] -= UL;
-        st_drop(&val[((long)ss * W + k) * C + pc], own ? Us - UL : Ls - UL);
-      }
-      ++k;
-    });
-    const double vol = m.V[c];
-    const double dd = m.rdt * rho[c] * vol + (d1 + d2);
-    const double ro = m.rdt * rho_old[c];
-    double dg[G], sr[G];
-#pragma unroll
-    for (int j = 0; j < G; ++j) {
-      const int s = g0 + j;
-      if (s >= S) break;
-      dg[j] = dd - dL[j];
-      sr[j] = ro * Y[s * C + c] * vol + vol * RR[s * C + c];
-    }
-    each_slot(m, tyY, c, [&](int b, int t) {
-      const double wu = bwY ? bwY[b] : (bphi[b] >= 0 ? 1.0 : 0.0);
-      const bool cp = bc_coupled(t);
-#pragma unroll
-      for (int j = 0; j < G; ++j) {
-        const int s = g0 + j;
-        if (s >= S) break;
-        if (s == inert) continue;
-        const int ss = s < inert ? s : s - 1;
-        const BCoef qc = bcoef_f(t, bY[s * B + b], wu, m.bdc[b], mxY, b, B, s);
-        const BCoef ql = bcoef_f(t, bY[s * B + b], m.bw[b], m.bdc[b], mxY, b, B, s);
-        const double gam = cp ? interp_b(m.bw[b], rhoD[s * C + c], nbrv(m, rhoD + s * C, brhoD + s * B, b)) : brhoD[s * B + b];
-        const double pG = gam * m.bmagSf[b];
-        const double icv = (bphi[b] * qc.vic + bphiUc[b] * qc.vic) - pG * ql.gic;
-        const double bcv = (-bphi[b] * qc.vbc + -bphiUc[b] * qc.vbc) - (-pG * ql.gbc);
-        dg[j] += icv;
-        if (cp) st_drop(&val[((long)ss * W + k) * C + pc], -bcv);
-        else sr[j] += bcv;
-      }
-      if (cp) ++k;
-    });
-#pragma unroll
-    for (int j = 0; j < G; ++j) {
-      const int s = g0 + j;
-      if (s >= S) break;
+    for (int s = 0; s < S; ++s) {
       if (s == inert) continue;
       const int ss = s < inert ? s : s - 1;
-      for (int kk = k; kk < W; ++kk) st_drop(&val[((long)ss * W + kk) * C + pc], 0.0);
-      st_drop(&dS[ss * Ce + pc], dg[j]);
-      st_drop(&rhs[ss * Ce + pc], sr[j]);
+      const double rn = rhoD[s * C + o2];
+      const double UL = dcf * ((own ? interp_f(w, rc[s], rn) : interp_f(w, rn, rc[s])) * ms);
+      dL[s] -= UL;
+      st_drop(&val[((long)ss * W + k) * C + pc], own ? Us - UL : Ls - UL);
     }
-  };
-  group(0);
+    ++k;
+  });
+  const double vol = m.V[c];
+  const double dd = m.rdt * rho[c] * vol + (d1 + d2);
+  const double ro = m.rdt * rho_old[c];
+  double dg[S], sr[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    dg[s] = dd - dL[s];
+    sr[s] = ro * Y[s * C + c] * vol + vol * RR[s * C + c];
+  }
+  each_slot(m, tyY, c, [&](int b, int t) {
+    const double wu = bwY ? bwY[b] : (bphi[b] >= 0 ? 1.0 : 0.0);
+    const bool cp = bc_coupled(t);
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      if (s == inert) continue;
+      const int ss = s < inert ? s : s - 1;
+      const BCoef qc = bcoef_f(t, bY[s * B + b], wu, m.bdc[b], mxY, b, B, s);
+      const BCoef ql = bcoef_f(t, bY[s * B + b], m.bw[b], m.bdc[b], mxY, b, B, s);
+      const double gam = cp ? interp_b(m.bw[b], rhoD[s * C + c], nbrv(m, rhoD + s * C, brhoD + s * B, b)) : brhoD[s * B + b];
+      const double pG = gam * m.bmagSf[b];
+      const double icv = (bphi[b] * qc.vic + bphiUc[b] * qc.vic) - pG * ql.gic;
+      const double bcv = (-bphi[b] * qc.vbc + -bphiUc[b] * qc.vbc) - (-pG * ql.gbc);
+      dg[s] += icv;
+      if (cp) st_drop(&val[((long)ss * W + k) * C + pc], -bcv);
+      else sr[s] += bcv;
+    }
+    if (cp) ++k;
+  });
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    if (s == inert) continue;
+    const int ss = s < inert ? s : s - 1;
+    for (int kk = k; kk < W; ++kk) st_drop(&val[((long)ss * W + kk) * C + pc], 0.0);
+    st_drop(&dS[ss * Ce + pc], dg[s]);
+    st_drop(&rhs[ss * Ce + pc], sr[s]);
+  }
 }
 
 

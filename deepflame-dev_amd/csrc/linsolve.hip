@@ -128,10 +128,8 @@ __global__ void k_ell_build(MeshView m, const int8_t* __restrict__ ty, Sys q, co
   const bool wv = vshared == 0 || (vshared == 1 && s == 0);
   for (int c = xcd_block() * blockDim.x + threadIdx.x; c < m.C; c += gridDim.x * blockDim.x) {
     const int pc = eopos ? eopos[c] : c;   // the row of c (even-odd layout) or c
-    const int cl = ecls_of(m, c);
     for (int k = 0; wv && k < W; ++k) {
-      int j, e;
-      erow(m, cl, k, c, j, e);
+      const int e = m.esrc[k * C + c];
       double v;
       if (e == PAD) v = 0.0;
       else if (e >= 0) v = (e & 1) ? U[e >> 1] : L[e >> 1];
@@ -1599,7 +1597,8 @@ void build_ell(Ctx& x) {
     }
   }
   // row classes: per cell the W (column offset, source code) pairs; coupled slots keep explicit sources
-  // (slot ids are not relative to the cell) and processor columns explicit columns
+  // (slot ids are not relative to the cell) and processor columns explicit columns. The source codes
+  // (2 kslot + own for the face at storage kslot * C + owner cell) only separate classes: no kernel reads them
   x.ell.ncls = 0;
   if (x.fslot && x.on("solver.row_classes")) {
     std::map<std::vector<int>, int> ids;
@@ -1629,12 +1628,11 @@ void build_ell(Ctx& x) {
     }
     if (ok && C > 0 && (long)ids.size() * W <= CT_MAX) {
       const int n = (int)ids.size();
-      std::vector<int> ctab((size_t)n * W), stab((size_t)n * W);
+      std::vector<int> ctab((size_t)n * W);
       for (auto& kv : ids)
-        for (int k = 0; k < W; ++k) { ctab[(size_t)kv.second * W + k] = kv.first[k]; stab[(size_t)kv.second * W + k] = kv.first[W + k]; }
+        for (int k = 0; k < W; ++k) ctab[(size_t)kv.second * W + k] = kv.first[k];
       x.ell.cls.upload(cls, x.stream);
       x.ell.ctab.upload(ctab, x.stream);
-      x.ell.stab.upload(stab, x.stream);
       x.ell.ncls = n;
     }
   }
