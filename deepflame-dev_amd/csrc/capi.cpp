@@ -277,7 +277,11 @@ void do_E(Ctx& x) {
 // UEqn's K, the cubic correction of hDiffCorrFlux from the YEqn preparation) read nothing the Y solve writes,
 // so they run on the side stream after both while the main stream solves the species; the rest of the
 // assembly needs the solved Y (the thermo's boundary energy gradient) and follows the Y solve
-void do_U_Y_E(Ctx& x) {
+// and a third: between the U solve and the join the main stream waits for the side stream's YEqn rows (about 0.55 ms
+// on the headline, k_y_assemble_ell running alone), so the first pressure corrector's HbyA is issued there (hbya:
+// step.hbya_early) -- it reads U, the U matrix and rAU as the U solve left them, none of which the Y or E equations or
+// correctThermo write, and nothing else reads or writes HbyA before the corrector
+void do_U_Y_E(Ctx& x, bool hbya = false) {
   if (!step_overlap(x)) { do_U(x); do_Y(x); do_E(x); return; }
   do_U_Y_fork(x);
   do_U(x);
@@ -288,6 +292,7 @@ void do_U_Y_E(Ctx& x) {
     e_assemble_front(x);
     DFMI_HIP(hipEventRecord(x.ev_e, x.stream2));
   }
+  if (hbya) u_hbya(x);
   DFMI_HIP(hipStreamWaitEvent(x.stream, x.ev_join, 0));
   do_Y_back(x);
   DFMI_HIP(hipStreamWaitEvent(x.stream, x.ev_e, 0));
@@ -295,10 +300,18 @@ void do_U_Y_E(Ctx& x) {
   do_E_back(x);
 }
 void do_p(Ctx& x) {
-  p_assemble(x);
+  // face-form PCG with the reused V-cycle: the solver's setup kernel does the cell pass too (pcg.fuse_setup)
+  const bool fuse = pcg_setup_fusable(x, x.solver["p"]);
+  p_assemble(x, !fuse);
   Matrix& A = x.mP;
-  solve_pcg(x, "p", A.lower, A.upper, A.diag, A.source, A.ic, A.bc, "p", x.f("p"), x.f("boundary_p"), x.solver["p"]);
+  solve_pcg(x, "p", A.lower, A.upper, A.diag, A.source, A.ic, A.bc, "p", x.f("p"), x.f("boundary_p"), x.solver["p"],
+            fuse);
   p_post_solve(x);
+}
+// step.hbya_early applies: the two-stream step on one rank (several ranks keep today's order: HbyA's field halo
+// stays behind the Y and E solves' exchanges)
+bool hbya_early(const Ctx& x) {
+  return step_overlap(x) && x.nranks == 1 && !halo_active(x) && x.on("step.hbya_early");
 }
 
 }  // namespace
@@ -675,14 +688,15 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
     copy_old(x);                    // preTimeStep
     if (x.chem.mode == 2) dnn_prepare(x);   // reacting cells of this step's T (read after the UEqn polls)
     rho_process(x, false);          // rhoEqn (first PIMPLE iteration)
-    do_U_Y_E(x);                    // UEqn, YEqn, EEqn (one rank: the chemistry and YEqn assembly beside the
+    const bool early = n_corr > 0 && hbya_early(x);   // the first corrector's HbyA right after the U solve
+    do_U_Y_E(x, early);             // UEqn, YEqn, EEqn (one rank: the chemistry and YEqn assembly beside the
                                     // UEqn, the EEqn assembly beside the Y solve)
     thermo_correct(x, false);       // correctThermo
     for (int i = 0; i < n_corr; ++i) {   // pEqn_GPU.H
       // rho = psi p: the first corrector's is what correctThermo just wrote (the same product of the same p and psi,
       // halo included); psip0 = psi p feeds only correctPsipRho, skipped below (the field is not updated here)
       if (i > 0) thermo_rho_from_psi(x);
-      u_hbya(x);
+      if (i > 0 || !early) u_hbya(x);
       // a later corrector may precondition with this step's first hierarchy; with amg.reuse_steps = k > 1 the first
       // corrector too, with the operators of up to k - 1 steps before (rebuilt when they are that old)
       const int keep = (int)x.opt("amg.reuse_steps");

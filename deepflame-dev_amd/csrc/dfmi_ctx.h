@@ -247,16 +247,22 @@ inline const OptDef* option_defs(int& n) {
     {"solver.row_classes", 1},        // solver rows decoded from one byte per cell where the mesh allows
     {"pcg.face_form", 1},             // one rank, hex box: the p operator read face-wise
     {"pcg.fuse_l0", 1},               // the PCG update fused with the V-cycle's level-0 first sweep
+    {"pcg.fuse_setup", 1},            // face-form PCG with the reused V-cycle: the pEqn's cell pass (diag, source), dS / rhs,
+                                      // the copy of p and the first residual in one launch (k_p_setup_fused)
     {"fv.hex_walk", 1},               // hex box in blockMesh order: face and neighbour indices computed
     {"fv.csr_walk", 0},               // assembly faces walked from the CSR lists instead of the gather rows
     {"fv.species_generic", 0},        // the species-chunked YEqn kernels at any species count (S > 16 always)
     {"fv.yprep_brick", 1},            // k_y_prep staging 16x4x4 bricks in LDS (hex walk)
+    {"fv.p_post_fused", 1},           // owner-slot face storage: k_p_cell_post also writes phi of the cell's owned faces
+                                      // (no k_p_flux_face pass)
     {"chem.method", 0},               // 0: ROS3 Rosenbrock, 1: linearly-implicit Euler extrapolation
     {"chem.generated", 1},            // compiled-in kinetics when the mechanism's fingerprint matches
     {"chem.binning", 2},              // cells launched in cost-binned order: 1 over the mesh, 2 inside 4096-cell tiles
     {"dnn.tuned_gemm", 1},            // DF-ODENet layers by the shape-tuned kernels (0: k_mlp_gemm for every layer)
     {"halo.overlap", 0},              // several ranks: solver halo exchanges on a comm stream while the interior rows run
                                       // (read per solve; DFMI_HALO_OVERLAP sets the default when the communicator is set)
+    {"step.hbya_early", 1},           // one rank, two-stream step: the first corrector's HbyA right after the U solve, while the
+                                      // main stream would wait for the side stream's YEqn rows (it reads what the U solve left)
     {"step.courant", 0},              // 1: dfmi_time_step ends with the Courant-number kernel and posts its record for
                                       // dfmi_courant_no (compressibleCourantNo.H, dfLowMachFoam.C:261); 0: nothing added
   };
@@ -497,7 +503,7 @@ void rho_process(Ctx& x, bool write_matrix);
 void u_assemble(Ctx& x);
 void u_post_solve(Ctx& x);
 void u_hbya(Ctx& x);
-void p_assemble(Ctx& x);
+void p_assemble(Ctx& x, bool cell_pass = true);   // cell_pass = false: solve_pcg's fused setup writes diag and source
 void p_post_solve(Ctx& x);
 void y_prep(Ctx& x, bool weights = true);   // weights = false: the caller formed the div(phi,Yi_h) weights
 void y_assemble(Ctx& x);
@@ -536,7 +542,10 @@ SolveStats solve_stats(Ctx& x, const std::string& eqn);
 double solver_work(Ctx& x, const std::string& eqn, bool reset);
 SolveStats solve_pcg(Ctx& x, const char* eqn, const double* lower, const double* upper, const double* diag,
                      const double* source, const double* ic, const double* bc, const char* type_field, double* xsol,
-                     double* bxsol, const SolverCfg& cfg);
+                     double* bxsol, const SolverCfg& cfg, bool fuse_setup = false);
+// the p solve about to run takes the face-form path with the reused V-cycle (no ELL values written) and the option
+// pcg.fuse_setup is on: the caller skips p_assemble's cell pass and passes fuse_setup = true
+bool pcg_setup_fusable(Ctx& x, const SolverCfg& cfg);
 // dnn.hip
 void dnn_upload(Ctx& x, int nmod, int nlayers, const int* dims, const float* params, const double* xmu,
                 const double* xstd, const double* ymu, const double* ystd, double T_react, double dt_infer);

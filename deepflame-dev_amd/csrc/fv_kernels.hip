@@ -1109,11 +1109,15 @@ __global__ void k_p_flux_slot(MeshView m, const int8_t* __restrict__ tyP, const 
   bphi[b] = bph[b] + fl;
 }
 // U = HbyA - rAU*grad(p); K; dpdt
-template <int WT>
-__global__ void k_p_cell_post(MeshView m, const int8_t* __restrict__ tyP, const double* __restrict__ p,
+// PHI: the walk also writes phi of the cell's owned faces, k_p_flux_face's expression with the p values it gathers
+// anyway (every internal face is owned by exactly one cell, so the two kernels write the same faces)
+template <int WT, bool PHI>
+__device__ __forceinline__ void p_cell_post(const MeshView& m, const int8_t* __restrict__ tyP, const double* __restrict__ p,
                               const double* __restrict__ bp, const double* __restrict__ p_old,
                               const double* __restrict__ H, const double* __restrict__ rAU, double* __restrict__ U,
-                              double* __restrict__ K, double* __restrict__ dpdt) {
+                              double* __restrict__ K, double* __restrict__ dpdt, const double* __restrict__ ph,
+                              const double* __restrict__ lower, const double* __restrict__ upper,
+                              double* __restrict__ phi) {
   const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
   if (c >= m.C) return;
   const long C = m.C, F = m.F, B = m.B;
@@ -1121,6 +1125,7 @@ __global__ void k_p_cell_post(MeshView m, const int8_t* __restrict__ tyP, const 
   const double pcc = p[c];
   each_face<WT>(m, c, [&](int f, int o2, bool own) {
     const double pn = p[o2];
+    if constexpr (PHI) { if (own) phi[f] = ph[f] + (upper[f] * pn - lower[f] * pcc); }
     const double pf = own ? interp_f(m.w[f], pcc, pn) : interp_f(m.w[f], pn, pcc);
 #pragma unroll
     for (int k = 0; k < 3; ++k) { const double v = m.Sf[k * F + f] * pf; if (own) g[k] += v; else g[k] -= v; }
@@ -1136,6 +1141,22 @@ __global__ void k_p_cell_post(MeshView m, const int8_t* __restrict__ tyP, const 
   for (int k = 0; k < 3; ++k) { u[k] = H[k * C + c] - rAU[c] * (g[k] / vol); U[k * C + c] = u[k]; }
   K[c] = 0.5 * (u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
   dpdt[c] = m.rdt * (p[c] - p_old[c]);
+}
+template <int WT>
+__global__ void k_p_cell_post(MeshView m, const int8_t* __restrict__ tyP, const double* __restrict__ p,
+                              const double* __restrict__ bp, const double* __restrict__ p_old,
+                              const double* __restrict__ H, const double* __restrict__ rAU, double* __restrict__ U,
+                              double* __restrict__ K, double* __restrict__ dpdt) {
+  p_cell_post<WT, false>(m, tyP, p, bp, p_old, H, rAU, U, K, dpdt, nullptr, nullptr, nullptr, nullptr);
+}
+template <int WT>
+__global__ void k_p_cell_post_phi(MeshView m, const int8_t* __restrict__ tyP, const double* __restrict__ p,
+                                  const double* __restrict__ bp, const double* __restrict__ p_old,
+                                  const double* __restrict__ H, const double* __restrict__ rAU, double* __restrict__ U,
+                                  double* __restrict__ K, double* __restrict__ dpdt, const double* __restrict__ ph,
+                                  const double* __restrict__ lower, const double* __restrict__ upper,
+                                  double* __restrict__ phi) {
+  p_cell_post<WT, true>(m, tyP, p, bp, p_old, H, rAU, U, K, dpdt, ph, lower, upper, phi);
 }
 __global__ void k_kinetic_slots(int B, const double* __restrict__ bU, double* __restrict__ bK) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2185,7 +2206,7 @@ void u_hbya(Ctx& x) {
   halo_fields(x, {"HbyA"});
 }
 
-void p_assemble(Ctx& x) {
+void p_assemble(Ctx& x, bool cell_pass) {
   Matrix& A = x.mP;
   MeshView m = x.view();
   {
@@ -2208,6 +2229,7 @@ void p_assemble(Ctx& x) {
          x.f("HbyA"), x.f("boundary_HbyA"), x.f("boundary_p"), x.f("boundary_rhorAUf"), x.f("boundary_phiHbyA"),
          A.ic.p, A.bc.p, mixbc(x, "p"), x.f("boundary_phi"), x.f("boundary_psi"), x.f("boundary_p_gamma"),
          x.f("boundary_p_vf"));
+  if (!cell_pass) return;   // solve_pcg's k_p_setup_fused forms diag and source (pcg.fuse_setup)
   LAUNCH_W(k_p_cell, x.C, m, x.st("p"), A.lower.p, x.f("phiHbyA"), x.f("boundary_phiHbyA"), x.f("p"), x.f("p_old"),
          x.f("psi"), x.f("rho"), x.f("rho_old"), A.diag.p, A.source.p);
 }
@@ -2217,11 +2239,18 @@ void p_post_solve(Ctx& x) {
   MeshView m = x.view();
   k_bc_correct(x, "p", x.f("p"), x.f("boundary_p"), 1);
   halo_fields(x, {"p"});
-  LAUNCH(k_p_flux_face, x.Fs, m, x.f("phiHbyA"), A.lower.p, A.upper.p, x.f("p"), x.f("phi"));
+  // owner-slot face storage: the cell walk of k_p_cell_post writes phi too (fv.p_post_fused), one gather of p at
+  // the neighbours instead of two
+  const bool fused = x.fslot && x.Fs > 0 && x.on("fv.p_post_fused");
+  if (!fused) LAUNCH(k_p_flux_face, x.Fs, m, x.f("phiHbyA"), A.lower.p, A.upper.p, x.f("p"), x.f("phi"));
   LAUNCH(k_p_flux_slot, x.B, m, x.st("p"), x.f("boundary_phiHbyA"), A.ic.p, A.bc.p, x.f("p"), x.f("boundary_p"),
          x.f("boundary_phi"));
-  LAUNCH_W(k_p_cell_post, x.C, m, x.st("p"), x.f("p"), x.f("boundary_p"), x.f("p_old"), x.f("HbyA"), x.f("rAU"),
-         x.f("U"), x.f("K"), x.f("dpdt"));
+  if (fused)
+    LAUNCH_W(k_p_cell_post_phi, x.C, m, x.st("p"), x.f("p"), x.f("boundary_p"), x.f("p_old"), x.f("HbyA"), x.f("rAU"),
+             x.f("U"), x.f("K"), x.f("dpdt"), x.f("phiHbyA"), A.lower.p, A.upper.p, x.f("phi"));
+  else
+    LAUNCH_W(k_p_cell_post, x.C, m, x.st("p"), x.f("p"), x.f("boundary_p"), x.f("p_old"), x.f("HbyA"), x.f("rAU"),
+             x.f("U"), x.f("K"), x.f("dpdt"));
   k_bc_correct(x, "U", x.f("U"), x.f("boundary_U"), 3);
   halo_fields(x, {"U"});
   LAUNCH(k_kinetic_slots, x.B, x.B, x.f("boundary_U"), x.f("boundary_K"));

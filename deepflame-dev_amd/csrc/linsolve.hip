@@ -672,6 +672,95 @@ __global__ void __launch_bounds__(TPB) k_cg_init(long C, int W, ColView col,
   block_partials<2>(acc, partial, 0);
 }
 
+// The pEqn's cell pass and the PCG's entry in one launch, for the face-form solve that reuses the V-cycle (no ELL
+// values are written there): per cell what k_p_cell (diag, source from the face coefficients, div(phiHbyA) and the
+// ddt terms), k_ell_build with no values (dS = diag + internalCoeffs, rhs = source + non-coupled boundaryCoeffs),
+// k_copy_x (xw = p) and k_cg_init<0, true> (r = rhs - A xw, z = r / dS, pa = pb = 0, the (r.z, r.r) block
+// partials) do one after the other -- the same expressions, each accumulator taking its faces and slots in the
+// same order, on k_cg_init's grid and loop, so every array and the partials keep their bits. The six face
+// coefficients are loaded once for both uses (the laplacian's lower and upper hold the same bits; k_p_face wrote
+// both in the assembly just before) and the neighbours' p comes from the field itself instead of its copy.
+struct PCell {
+  const int8_t* ty;
+  const double *ph, *bph, *p_old, *psi, *rho, *rho_old, *ic, *bc;
+  double *diag, *src;
+};
+__global__ void __launch_bounds__(TPB) k_p_setup_fused(MeshView m, PCell in, const double* __restrict__ p, CV v,
+                                                       double* partial, FaceOp<double> fo) {
+  double acc[2] = {0.0, 0.0};
+  const int nx = fo.nx, ny = fo.ny, nxy = fo.nx * fo.ny;
+  const int C = m.C;
+  for (int c = xcd_block() * blockDim.x + threadIdx.x; c < C; c += gridDim.x * blockDim.x) {
+    const int t = c / nx, i = c - t * nx, k = t / ny, j = t - k * ny;
+    const int hxp = i < nx - 1, hyp = j < ny - 1;
+    // faces in the sequential order: neighbour faces from the z-, y-, x- cells, then the owned +x, +y, +z
+    const bool has[6] = {k > 0, j > 0, i > 0, hxp != 0, hyp != 0, k < fo.nz - 1};
+    const int fc[6] = {(hxp + hyp) * C + (c - nxy), hxp * C + (c - nx), c - 1, c, hxp * C + c, (hxp + hyp) * C + c};
+    const int oc[6] = {c - nxy, c - nx, c - 1, c + 1, c + nx, c + nxy};
+    double a[6], fl[6], pn[6];
+#pragma unroll
+    for (int e = 0; e < 6; ++e)
+      if (has[e]) { a[e] = fo.up[fc[e]]; fl[e] = in.ph[fc[e]]; pn[e] = p[oc[e]]; }
+    const double pc = p[c];
+    double dL = 0.0, div = 0.0;
+#pragma unroll
+    for (int e = 0; e < 6; ++e)
+      if (has[e]) {
+        dL -= -a[e];
+        if (e >= 3) div += fl[e]; else div -= fl[e];
+      }
+    const int b0 = m.cbStart[c], b1 = m.cbStart[c + 1];
+    for (int s = b0; s < b1; ++s) {
+      const int b = m.cbSlot[s];
+      if (in.ty[b] == EMPTY) continue;
+      div += in.bph[b];
+    }
+    const double vol = m.V[c];
+    double dg = m.rdt * vol;
+    double sr = m.rdt * in.p_old[c] * vol;
+    const double APsi = -dg * pc + sr;
+    sr = sr - APsi;
+    sr = sr * in.psi[c];
+    dg = dg * in.psi[c];
+    sr = sr - vol * (m.rdt * (in.rho[c] - in.rho_old[c]));
+    sr = sr - div;
+    in.src[c] = sr;
+    double d = dg - dL;
+    in.diag[c] = d;
+    // dS and rhs (k_ell_build)
+    double r = sr;
+    for (int s = b0; s < b1; ++s) {
+      const int b = m.cbSlot[s];
+      if (in.ty[b] == EMPTY) continue;
+      d += in.ic[b];
+    }
+    for (int s = b0; s < b1; ++s) {
+      const int b = m.cbSlot[s];
+      const int tb = in.ty[b];
+      if (tb == EMPTY || bc_coupled(tb)) continue;
+      r += in.bc[b];
+    }
+    v.dS[c] = d;
+    v.rhs[c] = r;
+    v.xw[c] = pc;
+    // the first residual (k_cg_init, face_row's order: the six faces, then the coupled slots)
+    double ax = d * pc;
+#pragma unroll
+    for (int e = 0; e < 6; ++e)
+      if (has[e]) ax += a[e] * pn[e];
+    const int e1 = fo.csStart[c + 1];
+    for (int e = fo.csStart[c]; e < e1; ++e) {
+      const int b = fo.csSlot[e];
+      ax += -fo.bc[b] * p[fo.scol[b]];
+    }
+    const double rr = r - ax;
+    const double zz = rr / d;
+    v.r[c] = rr; v.z[c] = zz; v.pa[c] = 0.0; v.pb[c] = 0.0;
+    acc[0] += rr * zz; acc[1] += rr * rr;
+  }
+  block_partials<2>(acc, partial, 0);
+}
+
 // prologue: rz, res, convergence, beta; p_new = z + beta p_old (own and, on the fly, neighbours);
 // q = A p_new; partial p_new.q
 template <int WT, bool FF = false>
@@ -1929,9 +2018,31 @@ SolveStats solve_bicgstab(Ctx& x, const char* eqn, int nsys, const int* sys_map_
   return SolveStats{};
 }
 
+// the choices solve_pcg makes before its first launch
+struct PcgPath { bool amg, face, reuse; int novals; };
+static PcgPath pcg_path(const Ctx& x, const SolverCfg& cfg) {
+  PcgPath p;
+  p.amg = cfg.precond == 1;
+  // the symmetric p operator read face-wise on a hex box (FaceOp, one rank; pcg.face_form = 0: the ELL values)
+  p.face = x.hex[0] > 0 && x.fslot && x.nranks == 1 && !halo_active(x) && !small_solve(x) && x.on("pcg.face_form");
+  // a later corrector of the same step (amg.reuse): the V-cycle keeps the operators the first corrector built --
+  // a fixed SPD preconditioner of a matrix that changed by the density update only, so PCG still converges to
+  // this system's own tolerance; the fp32 rounding and Galerkin sums of one solve are saved
+  p.reuse = p.amg && x.amg.ready && x.amg.reuse_ok && x.on("amg.reuse") && x.nranks == 1;
+  // face-wise PCG with the reused V-cycle: nothing reads the ELL values, so they are not written -- only when
+  // the V-cycle's level 0 is the face-wise fp32 copy too (the fp64 V-cycle's level 0 reads the ELL values of
+  // THIS solve beside its diagonal, so they must be current)
+  p.novals = p.face && p.reuse && amg_l0_fusable(x) ? 2 : 0;
+  return p;
+}
+bool pcg_setup_fusable(Ctx& x, const SolverCfg& cfg) {
+  if (!x.ell.ready) build_ell(x);
+  return pcg_path(x, cfg).novals == 2 && x.on("pcg.fuse_setup");
+}
+
 SolveStats solve_pcg(Ctx& x, const char* eqn, const double* lower, const double* upper, const double* diag,
                      const double* source, const double* ic, const double* bc, const char* type_field, double* xsol,
-                     double* bxsol, const SolverCfg& cfg) {
+                     double* bxsol, const SolverCfg& cfg, bool fuse_setup) {
   (void)bxsol;
   if (!x.ell.ready) build_ell(x);
   CommTag _ct(x, std::string("pcg ") + eqn);
@@ -1954,26 +2065,29 @@ SolveStats solve_pcg(Ctx& x, const char* eqn, const double* lower, const double*
   const int8_t* ty = x.st(type_field);
   dim3 g(nblk), bl(TPB);
   Launch L{x, nblk, 1};
-  const bool amg = cfg.precond == 1;
+  const PcgPath path = pcg_path(x, cfg);
+  const bool amg = path.amg, face = path.face, reuse = path.reuse;
+  const int novals = path.novals;
   // multicolour DILU (amg.smoother = 1): k_pcg_small's in-workgroup V-cycle is Jacobi-only, so the solve takes the
   // batched path at any size
   const bool small = small_solve(x) && !(amg && amg_dilu_wanted(x));
-  // the symmetric p operator read face-wise on a hex box (FaceOp, one rank; pcg.face_form = 0: the ELL values)
-  const bool face = x.hex[0] > 0 && x.fslot && x.nranks == 1 && !halo_active(x) && !small_solve(x) && x.on("pcg.face_form");
-  // a later corrector of the same step (amg.reuse): the V-cycle keeps the operators the first corrector built --
-  // a fixed SPD preconditioner of a matrix that changed by the density update only, so PCG still converges to
-  // this system's own tolerance; the fp32 rounding and Galerkin sums of one solve are saved
-  const bool reuse = amg && x.amg.ready && x.amg.reuse_ok && x.on("amg.reuse") && x.nranks == 1;
-  // face-wise PCG with the reused V-cycle: nothing reads the ELL values, so they are not written -- only when
-  // the V-cycle's level 0 is the face-wise fp32 copy too (the fp64 V-cycle's level 0 reads the ELL values of
-  // THIS solve beside its diagonal, so they must be current)
-  const int novals = face && reuse && amg_l0_fusable(x) ? 2 : 0;
-  { KScope _ks(x, "k_ell_build"); hipLaunchKernelGGL(k_ell_build, g, bl, 0, x.stream, m, ty, q, (const int*)nullptr, W, x.ell.src.p, Ce, val, v.dS, v.rhs, novals); }
-  { KScope _ks(x, "k_copy_x"); hipLaunchKernelGGL(k_copy_x, g, bl, 0, x.stream, C, Ce, q, (const int*)nullptr, v.xw); }
-  DFMI_HIP(hipGetLastError());
   FaceOp<double> fo{};
   if (face) fo = FaceOp<double>{1, x.hex[0], x.hex[1], x.hex[2], C, upper, bc, x.ell.csStart.p, x.ell.csSlot.p,
                                 x.ell.scol.p};
+  if (fuse_setup) {
+    // the p system whose cell pass the caller left out (p_assemble(x, false)): diag, source, dS, rhs, xw and the
+    // first residual in one launch; the path is the one pcg_setup_fusable saw
+    DFMI_CHECK(novals == 2 && !small && diag == x.mP.diag.p && source == x.mP.source.p,
+               "solve_pcg: fused setup outside the face-form reuse path of the p equation");
+    PCell in{ty, x.f("phiHbyA"), x.f("boundary_phiHbyA"), x.f("p_old"), x.f("psi"), x.f("rho"), x.f("rho_old"), ic, bc,
+             x.mP.diag.p, x.mP.source.p};
+    KScope _ks(x, "k_p_setup_fused");
+    hipLaunchKernelGGL(k_p_setup_fused, g, bl, 0, x.stream, m, in, (const double*)xsol, v, q2, fo);
+  } else {
+    { KScope _ks(x, "k_ell_build"); hipLaunchKernelGGL(k_ell_build, g, bl, 0, x.stream, m, ty, q, (const int*)nullptr, W, x.ell.src.p, Ce, val, v.dS, v.rhs, novals); }
+    { KScope _ks(x, "k_copy_x"); hipLaunchKernelGGL(k_copy_x, g, bl, 0, x.stream, C, Ce, q, (const int*)nullptr, v.xw); }
+  }
+  DFMI_HIP(hipGetLastError());
   if (amg) {
     if (!x.amg.ready) amg_setup(x);
     x.amg.face = face && amg_l0_fusable(x) && x.amg.l0_sweeps == 1;
@@ -2006,7 +2120,7 @@ SolveStats solve_pcg(Ctx& x, const char* eqn, const double* lower, const double*
     record_stats(x, eqn, WS.scal.p, 1, pflag);
     return SolveStats{};
   }
-  dispatch_W(W, [&](auto wt) {
+  if (!fuse_setup) dispatch_W(W, [&](auto wt) {
     constexpr int WT = decltype(wt)::value;
     KScope _ks(x, "k_cg_init");
     if (face) hipLaunchKernelGGL((k_cg_init<0, true>), g, bl, 0, x.stream, C, W, x.ell.cols(), val, v, q2, fo);
