@@ -21,7 +21,8 @@
 // Layout: one cell per lane, 64-lane workgroups. Per-lane rate constants (they depend only on T,
 // which is frozen) and the per-lane S x S iteration matrix live in LDS as [entry][lane]
 // (bank-conflict free); state vectors live in registers (compile-time S). The mechanism arrays are
-// wave-uniform (scalar loads).
+// wave-uniform (scalar loads). That layout holds 4..12 species; 13..64 species run the cooperative kernel below
+// (k_chem_coop: several lanes per cell, the cell's matrix and rate constants in LDS once per cell).
 #include "dfmi_ctx.h"
 #include <cmath>
 #include <cstdlib>
@@ -718,6 +719,434 @@ __global__ void __launch_bounds__(LANES, 1) k_chem_gen(long n, const int* __rest
   if (steps < 0) atomicAdd(fail, 1);
 }
 
+// ---- cooperative kernel: 13..64 species (and any S >= 4 under chem.coop = 1)
+// The layout above keeps (3R + S^2) doubles per LANE in LDS: 355 KB per workgroup for DRM19 (21 / 84), 1 MB for
+// the 36-species gri30. Here TG lanes (16, 32 or 64; one cell never leaves its wave) integrate one cell, and the
+// cell's iteration matrix, rate constants and per-reaction rates live in LDS once per CELL:
+//   A [S][LD]  LD = S | 1: the lanes of a cell own rows, and a column walk (LU multipliers, the triangular solves)
+//              reads A[i][j] at stride LD doubles; ds_read_b64 banks are (byte / 4) % 64 per 32-lane half, so an odd
+//              LD puts 32 rows on 32 distinct bank pairs. The pivot row A[k][j] is one address: a broadcast.
+//   kf k0 ikc [R]  frozen with T;  ke Mf tb q [R]  per evaluation (effective rate constant, third-body factor, the
+//              [M]-derivative term of third-body / fall-off reactions, rate of progress);  C bv [S]  concentrations
+//              and the broadcast / reduction vector.
+// Lane l of a cell owns species rows l, l + TG, ... (RPL = 64 / TG of them at most, in registers) and reactions
+// l, l + TG, ... of the per-reaction pass. Every sum runs in a fixed order inside one lane -- production rates and
+// Jacobian rows over the species' reaction list (chem_upload builds it in k_chem's order: reaction, then slot),
+// norms and Qdot over the species index -- so there is no floating-point atomic, and a cell's bits depend on
+// neither its neighbours in the workgroup nor on where it was launched. A cell lives in one wave, so the kernel has
+// no workgroup barrier: cells that finish early, sit below Tmin or lie past the mesh just leave. Lanes of a cell
+// exchange data through LDS in program order (one wave executes its LDS instructions in order); cell_sync() keeps
+// the compiler from moving LDS accesses across the hand-over points.
+struct CoopList {
+  const int* off;      // [S + 1]
+  const int* ent;      // reaction * 8 + slot (0..2 reactant, 3..5 product), ordered by (reaction, slot)
+  const double* nu;    // signed stoichiometric coefficient (-nu_r, +nu_p)
+  // the same entries as self-contained records for the Jacobian rows, so that a row's walk is one stream of loads
+  // whose addresses do not depend on loaded values: rec_i [E][8] = reaction, its 6 species ids, reversible;
+  // rec_d [E][8] = signed coefficient, nu_r[3], nu_p[3], 0
+  const int* rec_i;
+  const double* rec_d;
+};
+struct CoopRec {
+  int r, ix[6], rev;
+  double nu, nr[3], np[3];
+};
+__device__ __forceinline__ CoopRec coop_rec(const CoopList& cl, int e) {
+  const int4* pi = reinterpret_cast<const int4*>(cl.rec_i + (long)e * 8);
+  const int4 a = pi[0], b = pi[1];
+  const double* pd = cl.rec_d + (long)e * 8;
+  CoopRec c;
+  c.r = a.x; c.ix[0] = a.y; c.ix[1] = a.z; c.ix[2] = a.w; c.ix[3] = b.x; c.ix[4] = b.y; c.ix[5] = b.z; c.rev = b.w;
+  c.nu = pd[0];
+  for (int j = 0; j < 3; ++j) { c.nr[j] = pd[1 + j]; c.np[j] = pd[4 + j]; }
+  return c;
+}
+
+__device__ __forceinline__ void cell_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// doubles of LDS one cell takes
+inline size_t coop_cell_doubles(int S, int R) { return (size_t)S * (S | 1) + 7 * (size_t)R + 2 * (size_t)S; }
+
+template <int TG> struct Coop {
+  static constexpr int RPL = LANES / TG;   // rows a lane can own (S <= 64)
+  int S, R, LD, l;
+  double *A, *kf, *k0, *ikc, *ke, *Mf, *tb, *q, *C, *bv;
+  __device__ __forceinline__ int row(int s) const { return l + s * TG; }
+
+  // kf, k0, 1 / Kc of every reaction at the cell's (frozen) temperature
+  __device__ __forceinline__ void rate_constants(const ChemMech& m, double T) const {
+    const double lnT = log(T), rT = 1.0 / T;
+    cell_sync();
+    for (int i = l; i < S; i += TG) {   // g_i / RT from NASA7
+      const double* row = m.nasa + i * 15;
+      const double* a = T > row[0] ? row + 1 : row + 8;
+      const double h = a[0] + a[1] * T / 2 + a[2] * T * T / 3 + a[3] * T * T * T / 4 + a[4] * T * T * T * T / 5 + a[5] / T;
+      const double s = a[0] * lnT + a[1] * T + a[2] * T * T / 2 + a[3] * T * T * T / 3 + a[4] * T * T * T * T / 4 + a[6];
+      bv[i] = h - s;
+    }
+    cell_sync();
+    for (int r = l; r < R; r += TG) {
+      const int* id = m.idata + r * 8;
+      const int* ix = m.irs + r * 6;
+      const double* d = m.dd + (long)r * m.ndd;
+      kf[r] = d[0] * exp(d[1] * lnT - d[2] * rT);
+      k0[r] = id[0] >= 2 ? d[9] * exp(d[10] * lnT - d[11] * rT) : 0.0;
+      double ik = 0.0;
+      if (id[1]) {
+        double dG = 0.0, dnu = 0.0;
+        for (int k = 0; k < 3; ++k) {
+          const int ip = ix[3 + k], ir = ix[k];
+          if (ip >= 0) { dG += d[6 + k] * bv[ip]; dnu += d[6 + k]; }
+          if (ir >= 0) { dG -= d[3 + k] * bv[ir]; dnu -= d[3 + k]; }
+        }
+        ik = exp(dG - dnu * log(P_ATM / (RU * T)));
+      }
+      ikc[r] = ik;
+    }
+    cell_sync();
+  }
+
+  // per-reaction pass at the concentrations in C: q; with jac also ke, Mf and tb (what the Jacobian rows need)
+  __device__ __forceinline__ void reactions(const ChemMech& m, double T, bool jac) const {
+    cell_sync();
+    for (int r = l; r < R; r += TG) {
+      const int* id = m.idata + r * 8;
+      const int* ix = m.irs + r * 6;
+      const double* d = m.dd + (long)r * m.ndd;
+      const int type = id[0];
+      const double kinf = kf[r];
+      double k = kinf, mf = 1.0, M = 0.0, F = 1.0, Pr = 0.0, corr = 0.0;
+      if (type != 0) {
+        for (int i = 0; i < S; ++i) M += d[17 + i] * C[i];
+        if (type == 1) mf = M;
+        else {
+          Pr = k0[r] * M / kinf;
+          if (type == 3) {
+            const double a = d[12], T3 = d[13], T1 = d[14], T2 = d[15];
+            const double Fc = (1 - a) * exp(-T / T3) + a * exp(-T / T1) + (id[4] ? exp(-T2 / T) : 0.0);
+            const double lFc = log10(fmax(Fc, 1e-300));
+            const double c = -0.4 - 0.67 * lFc, n = 0.75 - 1.27 * lFc;
+            const double lPr = log10(fmax(Pr, 1e-300));
+            const double u = n - 0.14 * (lPr + c);
+            const double f1 = (lPr + c) / u;
+            F = exp10(lFc / (1 + f1 * f1));
+            corr = F * 2.0 * lFc * f1 * n / ((1.0 + Pr) * (1.0 + f1 * f1) * (1.0 + f1 * f1) * u * u);
+          }
+          k = kinf * Pr / (1 + Pr) * F;
+        }
+      }
+      const double ik = id[1] ? ikc[r] : 0.0;
+      // forward / backward rates with the effective constant (f, b) and with k_inf (fi, bi: the fall-off derivative)
+      double f = k, b = id[1] ? k * ik : 0.0, fi = kinf, bi = id[1] ? kinf * ik : 0.0;
+      for (int j = 0; j < 3; ++j) {
+        if (ix[j] >= 0) { const double v = ipow(C[ix[j]], d[3 + j]); f *= v; fi *= v; }
+        if (ix[3 + j] >= 0) { const double v = ipow(C[ix[3 + j]], d[6 + j]); b *= v; bi *= v; }
+      }
+      q[r] = mf * (f - b);
+      if (jac) {
+        ke[r] = k;
+        Mf[r] = mf;
+        double t = 0.0;
+        if (type == 1) t = f - b;
+        else if (type >= 2) t = k0[r] / kinf * (F / ((1.0 + Pr) * (1.0 + Pr)) - corr) * (fi - bi);
+        tb[r] = t;
+      }
+    }
+    cell_sync();
+  }
+
+  // dC_i/dt of the rows this lane owns, from q
+  __device__ __forceinline__ void production(const CoopList& cl, double (&w)[RPL]) const {
+#pragma unroll
+    for (int s = 0; s < RPL; ++s) {
+      w[s] = 0.0;
+      const int i = row(s);
+      if (i < S)
+        for (int e = cl.off[i]; e < cl.off[i + 1]; ++e) w[s] += cl.nu[e] * q[cl.ent[e] >> 3];
+    }
+  }
+
+  // rows of A = I - h J this lane owns (J = d(dC/dt)/dC: mass action, third-body factors, fall-off [M] dependence)
+  __device__ __forceinline__ void build_rows(const ChemMech& m, const CoopList& cl, double h) const {
+#pragma unroll
+    for (int s = 0; s < RPL; ++s) {
+      const int i = row(s);
+      if (i >= S) continue;
+      double* Ai = A + i * LD;
+      for (int j = 0; j < S; ++j) Ai[j] = (i == j) ? 1.0 : 0.0;
+      const int e0 = cl.off[i], e1 = cl.off[i + 1];
+      CoopRec nx = coop_rec(cl, e0);   // the lists are padded by one record
+      for (int e = e0; e < e1; ++e) {
+        const CoopRec c = nx;
+        nx = coop_rec(cl, e + 1);      // the next record's loads fly while this one is worked on
+        const int r = c.r;
+        const double nu = c.nu;
+        const int* ix = c.ix;
+        const double k = ke[r], mf = Mf[r];
+        const double kb = c.rev ? k * ikc[r] : 0.0;
+        double cr[3], cp[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          cr[j] = ix[j] >= 0 ? C[ix[j]] : 1.0;
+          cp[j] = ix[3 + j] >= 0 ? C[ix[3 + j]] : 1.0;
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          if (ix[a] >= 0) {
+            double t = k;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) if (ix[j] >= 0) t *= (j == a) ? dipow(cr[j], c.nr[j]) : ipow(cr[j], c.nr[j]);
+            const double dq = mf * t;
+            if (dq != 0.0) Ai[ix[a]] -= h * nu * dq;
+          }
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          if (ix[3 + a] >= 0) {
+            double u = kb;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) if (ix[3 + j] >= 0) u *= (j == a) ? dipow(cp[j], c.np[j]) : ipow(cp[j], c.np[j]);
+            const double dq = -mf * u;
+            if (dq != 0.0) Ai[ix[3 + a]] -= h * nu * dq;
+          }
+        }
+        const double* d = m.dd + (long)r * m.ndd;
+        const double t = tb[r];
+        if (t != 0.0) {
+          const double* ef = d + 17;
+          int j = 0;
+          for (; j + 4 <= S; j += 4) {   // loads first, as in lu()
+            const double a0 = Ai[j], a1 = Ai[j + 1], a2 = Ai[j + 2], a3 = Ai[j + 3];
+            const double f0 = ef[j], f1 = ef[j + 1], f2 = ef[j + 2], f3 = ef[j + 3];
+            Ai[j] = a0 - h * nu * f0 * t; Ai[j + 1] = a1 - h * nu * f1 * t;
+            Ai[j + 2] = a2 - h * nu * f2 * t; Ai[j + 3] = a3 - h * nu * f3 * t;
+          }
+          for (; j < S; ++j) Ai[j] -= h * nu * ef[j] * t;
+        }
+      }
+    }
+    cell_sync();
+  }
+
+  // in-place LU without pivoting, by row ownership; false if singular (the same for every lane of the cell)
+  __device__ __forceinline__ bool lu() const {
+    for (int k = 0; k < S; ++k) {
+      cell_sync();   // row k is final: its owner last touched it in step k - 1
+      const double* Ak = A + k * LD;
+      const double p = Ak[k];
+      if (!(fabs(p) > 1e-300)) return false;
+      const double ip = 1.0 / p;
+#pragma unroll
+      for (int s = 0; s < RPL; ++s) {
+        const int i = row(s);
+        if (i > k && i < S) {
+          double* Ai = A + i * LD;
+          const double f = Ai[k] * ip;
+          Ai[k] = f;
+          int j = k + 1;
+          for (; j + 4 <= S; j += 4) {   // four columns per round: the LDS reads are issued before the first write
+            const double a0 = Ai[j], a1 = Ai[j + 1], a2 = Ai[j + 2], a3 = Ai[j + 3];
+            const double p0 = Ak[j], p1 = Ak[j + 1], p2 = Ak[j + 2], p3 = Ak[j + 3];
+            Ai[j] = a0 - f * p0; Ai[j + 1] = a1 - f * p1; Ai[j + 2] = a2 - f * p2; Ai[j + 3] = a3 - f * p3;
+          }
+          for (; j < S; ++j) Ai[j] -= f * Ak[j];
+        }
+      }
+    }
+    cell_sync();
+    return true;
+  }
+
+  // L U x = b, column by column: the owner of row j publishes its finished entry, every later (earlier) row takes it
+  __device__ __forceinline__ void solve(double (&b)[RPL]) const {
+    for (int j = 0; j < S; ++j) {
+      cell_sync();
+#pragma unroll
+      for (int s = 0; s < RPL; ++s) if (row(s) == j) bv[j] = b[s];
+      cell_sync();
+      const double bj = bv[j];
+#pragma unroll
+      for (int s = 0; s < RPL; ++s) {
+        const int i = row(s);
+        if (i > j && i < S) b[s] -= A[i * LD + j] * bj;
+      }
+    }
+    for (int j = S - 1; j >= 0; --j) {
+      cell_sync();
+#pragma unroll
+      for (int s = 0; s < RPL; ++s) if (row(s) == j) { b[s] = b[s] / A[j * LD + j]; bv[j] = b[s]; }
+      cell_sync();
+      const double bj = bv[j];
+#pragma unroll
+      for (int s = 0; s < RPL; ++s) {
+        const int i = row(s);
+        if (i < j) b[s] -= A[i * LD + j] * bj;
+      }
+    }
+  }
+
+  // sum over the species index, in order, of the values the row owners hold (every lane gets the same bits)
+  __device__ __forceinline__ double ordered_sum(const double (&v)[RPL]) const {
+    cell_sync();
+#pragma unroll
+    for (int s = 0; s < RPL; ++s) if (row(s) < S) bv[row(s)] = v[s];
+    cell_sync();
+    double a = 0.0;
+    for (int i = 0; i < S; ++i) a += bv[i];
+    return a;
+  }
+
+  __device__ __forceinline__ void publish(const double (&v)[RPL]) const {   // C = v
+    cell_sync();
+#pragma unroll
+    for (int s = 0; s < RPL; ++s) if (row(s) < S) C[row(s)] = v[s];
+  }
+};
+
+// the cell slot (position in launch order) of this lane's cell: chem_thread's tile interleave for workgroups of
+// NCB cells -- XCD x's k-th workgroup takes block k % TBC of tile (k / TBC) * 8 + x, TBC = blocks per tile
+template <int TG, int NCB> __device__ inline long coop_slot(int tiled) {
+  constexpr int TBC = BCELLS * GRP / NCB;
+  long b = blockIdx.x;
+  if (tiled) { const long x = b % 8, k = b / 8; b = ((k / TBC) * 8 + x) * TBC + k % TBC; }
+  return b * NCB + threadIdx.x / TG;
+}
+
+template <int TG, int NCB>
+__global__ void __launch_bounds__(TG * NCB) k_chem_coop(long n, const int* __restrict__ perm, ChemMech m, CoopList cl, int S,
+    const double* __restrict__ Tf, const double* __restrict__ pf, const double* __restrict__ rhof,
+    const double* __restrict__ Yf, double dt, double rtol, double atol, double Tmin, int max_steps,
+    double* __restrict__ RR, double* __restrict__ stats, int* __restrict__ fail, int tiled, const double* __restrict__ hc,
+    double* __restrict__ Qdot) {
+  static_assert(LANES % TG == 0 && (TG * NCB) % LANES == 0, "a cell must not straddle waves");
+  constexpr int RPL = Coop<TG>::RPL;
+  constexpr double g = 0.43586652150845899941601945119356;
+  constexpr double c21 = -0.10156171083877702091975600115545e1, c31 = 0.40759956452537699824805835358067e1,
+                   c32 = 0.92076794298330791242156818474003e1;
+  constexpr double m1 = 1.0, m2 = 0.61697947043828245592553615689730e1, m3 = -0.42772256543218573326238373806514;
+  constexpr double e1 = 0.5, e2 = -0.29079558716805469821718236208017e1, e3 = 0.22354069897811569627360909276199;
+  extern __shared__ double lds[];
+  const int R = m.R;
+  Coop<TG> L;
+  L.S = S; L.R = R; L.LD = S | 1; L.l = threadIdx.x % TG;
+  {
+    double* base = lds + (size_t)(threadIdx.x / TG) * ((size_t)S * L.LD + 7 * (size_t)R + 2 * (size_t)S);
+    L.A = base; base += S * L.LD;
+    L.kf = base; L.k0 = base + R; L.ikc = base + 2 * R; L.ke = base + 3 * R; L.Mf = base + 4 * R; L.tb = base + 5 * R;
+    L.q = base + 6 * R; base += 7 * R;
+    L.C = base; L.bv = base + S;
+  }
+  const long t = coop_slot<TG, NCB>(tiled);
+  if (t >= (perm ? (n + GRP - 1) / GRP * GRP : n)) return;   // no workgroup barrier below: a cell is inside one wave
+  const long c = bin_cell(perm, t);
+  if (c >= n) return;
+  const double T = Tf[c];
+  double y[RPL], Wl[RPL];
+  double rho;
+  {   // reactor_state (setState_TPY), sums in species order
+    double a[RPL];
+#pragma unroll
+    for (int s = 0; s < RPL; ++s) {
+      const int i = L.row(s);
+      a[s] = i < S ? fmax(Yf[(long)i * n + c], 0.0) : 0.0;
+      Wl[s] = i < S ? m.W[i] : 1.0;
+    }
+    const double iys = 1.0 / L.ordered_sum(a);
+    double b[RPL];
+#pragma unroll
+    for (int s = 0; s < RPL; ++s) b[s] = a[s] * iys / Wl[s];
+    const double sw = L.ordered_sum(b);
+    rho = pf[c] / (sw * RU * T);
+#pragma unroll
+    for (int s = 0; s < RPL; ++s) y[s] = rho * (a[s] * iys) / Wl[s];
+  }
+  int steps = 0, rejects = 0;
+  double hnext = 0.0;   // the step the integration would take next
+  if (T >= Tmin) {
+    L.rate_constants(m, T);
+    // first step: the size the previous solve of this cell ended with (OpenFOAM's per-cell deltaTChem)
+    const double hp = stats[2 * n + c];
+    double tt = 0.0, h = hp > 0.0 ? fmin(dt, hp) : dt;
+    while (tt < dt) {
+      if (steps + rejects >= max_steps) { steps = -1; break; }
+      if (tt + h > dt) h = dt - tt;
+      const double hg = h * g, rh = 1.0 / h;
+      double f0[RPL], k1[RPL], k2[RPL], k3[RPL], v[RPL];
+      L.publish(y);
+      L.reactions(m, T, true);
+      L.production(cl, f0);
+      L.build_rows(m, cl, hg);
+      bool ok = L.lu();
+      double err = 0.0;
+      if (ok) {   // ROS3 (the stages of ros3 above)
+#pragma unroll
+        for (int s = 0; s < RPL; ++s) k1[s] = hg * f0[s];
+        L.solve(k1);
+#pragma unroll
+        for (int s = 0; s < RPL; ++s) v[s] = y[s] + k1[s];
+        L.publish(v);
+        L.reactions(m, T, false);
+        L.production(cl, f0);   // f of stage 2 (stage 3 reuses it)
+#pragma unroll
+        for (int s = 0; s < RPL; ++s) k2[s] = hg * (f0[s] + c21 * rh * k1[s]);
+        L.solve(k2);
+#pragma unroll
+        for (int s = 0; s < RPL; ++s) k3[s] = hg * (f0[s] + rh * (c31 * k1[s] + c32 * k2[s]));
+        L.solve(k3);
+        double e2s[RPL];
+#pragma unroll
+        for (int s = 0; s < RPL; ++s) {
+          v[s] = y[s] + m1 * k1[s] + m2 * k2[s] + m3 * k3[s];
+          const double er = e1 * k1[s] + e2 * k2[s] + e3 * k3[s];
+          const double e = er / (atol * (rho / Wl[s]) + rtol * fmax(fabs(y[s]), fabs(v[s])));   // weighted RMS norm
+          e2s[s] = L.row(s) < S ? e * e : 0.0;
+        }
+        err = sqrt(L.ordered_sum(e2s) / S);
+        if (!(err == err)) ok = false;
+      }
+      if (ok && err <= 1.0) {
+#pragma unroll
+        for (int s = 0; s < RPL; ++s) y[s] = v[s];
+        tt += h;
+        ++steps;
+        const double fac = err > 0.0 ? 0.9 * pow(err, -1.0 / 3.0) : 5.0;
+        h = h * fmin(5.0, fmax(0.2, fac));
+      } else {
+        ++rejects;
+        const double fac = ok ? 0.9 * pow(err, -1.0 / 3.0) : 0.25;
+        h = h * fmin(0.5, fmax(0.1, fac));
+      }
+    }
+    if (steps >= 0) hnext = h;
+  }
+  const double rho_rr = rhof[c];
+  double qh[RPL];
+#pragma unroll
+  for (int s = 0; s < RPL; ++s) {
+    const int i = L.row(s);
+    qh[s] = 0.0;
+    if (i < S) {
+      const double Yn = y[s] * Wl[s] / rho;
+      const double rr = T >= Tmin ? (Yn - Yf[(long)i * n + c]) * rho_rr / dt : 0.0;
+      RR[(long)i * n + c] = rr;
+      qh[s] = hc[i] * rr;
+    }
+  }
+  // Qdot = -sum_i hc_i RR_i in species order (dfChemistryModel.C:771): q -= hc_i rr_i from 0 is -(ordered sum)
+  const double qs = L.ordered_sum(qh);
+  if (L.l == 0) {
+    Qdot[c] = -qs;
+    stats[c] = steps;
+    stats[n + c] = rejects;
+    if (hnext > 0.0) stats[2 * n + c] = hnext;
+    if (steps < 0) atomicAdd(fail, 1);   // integer count, one lane per cell
+  }
+}
+
 // FNV-1a over the packed mechanism, NASA7 rows and molecular weights (dfmi/chem_codegen.py:fingerprint)
 unsigned long long fnv(unsigned long long h, const void* p, size_t n) {
   const unsigned char* b = static_cast<const unsigned char*>(p);
@@ -742,17 +1171,56 @@ void chem_upload(Ctx& x, int R, const int* idata, const int* irs, const double* 
     for (int k = 0; k < 6; ++k) DFMI_CHECK(irs[r * 6 + k] < x.S, "chemistry: species index out of range");
     DFMI_CHECK(idata[r * 8] >= 0 && idata[r * 8] <= 3, "chemistry: unknown reaction type");
   }
+  // the cooperative kernel's per-species reaction lists, in k_chem's accumulation order (reaction, then slot:
+  // reactants 0..2, products 3..5), with the signed stoichiometric coefficient
+  std::vector<int> off(x.S + 1, 0), ent;
+  std::vector<double> nu;
+  for (int i = 0; i < x.S; ++i) {
+    for (int r = 0; r < R; ++r)
+      for (int a = 0; a < 6; ++a)
+        if (irs[r * 6 + a] == i) {
+          ent.push_back(r * 8 + a);
+          const double* d = dd + (size_t)r * h.ndd;
+          nu.push_back(a < 3 ? -d[3 + a] : d[6 + (a - 3)]);
+        }
+    off[i + 1] = (int)ent.size();
+  }
+  std::vector<int> rec_i((ent.size() + 1) * 8, -1);       // one padding record: the row walk reads one ahead
+  std::vector<double> rec_d((ent.size() + 1) * 8, 0.0);
+  for (size_t e = 0; e < ent.size(); ++e) {
+    const int r = ent[e] >> 3;
+    const double* d = dd + (size_t)r * h.ndd;
+    rec_i[e * 8] = r;
+    for (int a = 0; a < 6; ++a) rec_i[e * 8 + 1 + a] = irs[r * 6 + a];
+    rec_i[e * 8 + 7] = idata[r * 8 + 1];
+    rec_d[e * 8] = nu[e];
+    for (int j = 0; j < 6; ++j) rec_d[e * 8 + 1 + j] = d[3 + j];
+  }
+  rec_i[ent.size() * 8] = 0;   // the padding record is loaded, never used; keep its reaction index valid
+  if (ent.empty()) { ent.push_back(0); nu.push_back(0.0); }
+  h.sp_off.upload(off.data(), off.size(), x.stream);
+  h.sp_ent.upload(ent.data(), ent.size(), x.stream);
+  h.sp_nu.upload(nu.data(), nu.size(), x.stream);
+  h.sp_rec_i.upload(rec_i.data(), rec_i.size(), x.stream);
+  h.sp_rec_d.upload(rec_d.data(), rec_d.size(), x.stream);
   DFMI_HIP(hipStreamSynchronize(x.stream));
   h.ready = true;
 }
+
+namespace {
+// lanes per cell of the cooperative kernel by species count (profiles/chem_coop.json)
+int coop_lanes_for(int S) { return S <= 16 ? 16 : (S <= 32 ? 32 : 64); }
+}  // namespace
 
 void chem_solve(Ctx& x, double dt, const char* rho_field) {
   Chem& h = x.chem;
   DFMI_CHECK(h.ready, "chemistry mechanism not set (dfmi_chem_set_mechanism)");
   DFMI_CHECK(x.thermo.S == x.S, "chemistry needs the thermo coefficients (NASA7, W)");
   ChemMech m{h.R, h.ndd, h.idata.p, h.irs.p, h.dd.p, x.thermo.dnasa.p, x.thermo.dW.p};
+  DFMI_CHECK(x.S >= 4 && x.S <= 64, "chemistry: species count " + std::to_string(x.S) + " outside 4..64");
+  const bool coop = x.S > 12 || x.on("chem.coop");
   const size_t lds = ((size_t)3 * h.R + (size_t)x.S * x.S) * LANES * sizeof(double);
-  DFMI_CHECK(lds <= 160 * 1024, "chemistry: mechanism too large for the LDS layout");
+  DFMI_CHECK(coop || lds <= 160 * 1024, "chemistry: mechanism too large for the LDS layout");
   double* stats = x.f("chem_stats");
   const double* rho_rr = x.f(rho_field);
   if (h.fail.n == 0) h.fail.alloc(1);
@@ -761,6 +1229,8 @@ void chem_solve(Ctx& x, double dt, const char* rho_field) {
   h.bin = (int)x.opt("chem.binning");
   const long ng = (x.C + GRP - 1) / GRP;   // binning groups
   const int tiled = h.bin == 2;
+  DFMI_CHECK(!(coop && h.method == 1), "chemistry: extrapolation is not available above 12 species (chem.method = 1 "
+                                       "with the cooperative kernel; use chem.method = 0)");
   long nblk = blocks_for(h.bin ? ng * GRP : (long)x.C, LANES);
   if (tiled) nblk = (nblk + 8L * TILE_B - 1) / (8L * TILE_B) * (8L * TILE_B);   // whole groups of 8 tiles
   const dim3 g((unsigned)nblk);
@@ -774,7 +1244,7 @@ void chem_solve(Ctx& x, double dt, const char* rho_field) {
   fp = fnv(fp, x.thermo.nasa.data(), x.thermo.nasa.size() * 8);
   fp = fnv(fp, x.thermo.W.data(), x.thermo.W.size() * 8);
   h.generated = 0;
-  if (x.on("chem.generated") && h.method == 0) {
+  if (!coop && x.on("chem.generated") && h.method == 0) {
     if (fp == ChemGen_burke9::FINGERPRINT) h.generated = 1;
     else if (fp == ChemGen_es80::FINGERPRINT) h.generated = 2;
   }
@@ -790,6 +1260,41 @@ void chem_solve(Ctx& x, double dt, const char* rho_field) {
     hipLaunchKernelGGL(k_bin_scatter, dim3(nb), dim3(BCB), 0, x.stream, (long)x.C, (const double*)stats, nb,
                        (const int*)h.bcnt.p, h.perm.p);
     perm = h.perm.p;
+  }
+  if (coop) {
+    int tg = (int)x.opt("chem.coop_lanes");
+    DFMI_CHECK(tg == 0 || tg == 16 || tg == 32 || tg == 64, "chem.coop_lanes must be 0 (by species count), 16, 32 or 64");
+    const size_t cell = coop_cell_doubles(x.S, h.R) * sizeof(double);
+    if (tg == 0) {
+      tg = coop_lanes_for(x.S);
+      while (tg < LANES && cell * (LANES / tg) > 160 * 1024) tg *= 2;   // fewer cells per workgroup until they fit
+    }
+    const int ncb = LANES / tg;   // one wave per workgroup
+    const size_t clds = cell * ncb;
+    DFMI_CHECK(clds <= 160 * 1024, "chemistry: " + std::to_string(x.S) + " species / " + std::to_string(h.R) +
+                                       " reactions need " + std::to_string(clds) + " B of LDS per workgroup at " +
+                                       std::to_string(tg) + " lanes per cell (160 KiB available)");
+    const long slots = h.bin ? ng * GRP : (long)x.C;
+    long cb = blocks_for(slots, ncb);
+    const long tbc = (long)BCELLS * GRP / ncb;
+    if (tiled) cb = (cb + 8 * tbc - 1) / (8 * tbc) * (8 * tbc);   // whole groups of 8 tiles
+    DFMI_CHECK(cb < (1L << 31), "chemistry: too many cells for one launch");
+    CoopList cl{h.sp_off.p, h.sp_ent.p, h.sp_nu.p, h.sp_rec_i.p, h.sp_rec_d.p};
+    KScope _ks(x, "k_chem");
+#define COOP(TG, NCB)                                                                                               \
+  do {                                                                                                              \
+    DFMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chem_coop<TG, NCB>),                             \
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds));                           \
+    hipLaunchKernelGGL((k_chem_coop<TG, NCB>), dim3((unsigned)cb), dim3(TG * NCB), clds, x.stream, (long)x.C, perm, m, \
+                       cl, x.S, x.f("T"), x.f("p"), rho_rr, x.f("Y"), dt, h.rtol, h.atol, h.Tmin, h.max_steps,     \
+                       x.f("RR"), stats, h.fail.p, tiled, x.thermo.dhc.p, x.f("Qdot"));                            \
+  } while (0)
+    if (tg == 16) COOP(16, 4); else if (tg == 32) COOP(32, 2); else COOP(64, 1);
+#undef COOP
+    DFMI_HIP(hipGetLastError());
+    h.generated = -1;
+    chem_fail_snapshot(x);
+    return;
   }
   if (h.generated) {
     KScope _ks(x, "k_chem");
@@ -813,7 +1318,7 @@ void chem_solve(Ctx& x, double dt, const char* rho_field) {
     case 4: CALL(4); break; case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break;
     case 8: CALL(8); break; case 9: CALL(9); break; case 10: CALL(10); break; case 11: CALL(11); break;
     case 12: CALL(12); break;
-    default: throw Error("chemistry: species count " + std::to_string(x.S) + " not instantiated (4..12)");
+    default: throw Error("chemistry: species count " + std::to_string(x.S) + " not instantiated");
   }
 #undef CALL
   DFMI_HIP(hipGetLastError());

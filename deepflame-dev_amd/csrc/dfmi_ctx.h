@@ -134,9 +134,13 @@ struct Chem {
   double rtol = 1e-6, atol = 1e-10, Tmin = 0.0;   // CVODE settings of the reference (CanteraTorchProperties)
   int max_steps = 100000;
   int method = 0;               // 0 ROS3 Rosenbrock, 1 linearly-implicit Euler extrapolation
-  int generated = 0;            // last solve used a compiled-in mechanism (chem_gen_*.inc): 1 burke9, 2 es80
+  int generated = 0;            // last solve used a compiled-in mechanism (chem_gen_*.inc): 1 burke9, 2 es80; -1: the cooperative kernel
   int bin = 2;                  // order cells by the previous solve's step count (option chem.binning: 0 natural order, 1 whole mesh, 2 per tile)
   DevBuf<int> perm, bcnt;       // cost-binned cell order; per-block bucket counts / offsets
+  DevBuf<int> sp_off, sp_ent;   // cooperative kernel: per-species reaction lists (offsets [S + 1], reaction * 8 + slot)
+  DevBuf<double> sp_nu;         // and their signed stoichiometric coefficients
+  DevBuf<int> sp_rec_i;         // the same entries as self-contained records (chem.hip CoopList)
+  DevBuf<double> sp_rec_d;
   std::vector<int> h_idata, h_irs;
   std::vector<double> h_dd;
   DevBuf<int> fail;             // cells of the last solve that hit max_steps (device counter)
@@ -258,6 +262,8 @@ inline const OptDef* option_defs(int& n) {
     {"chem.method", 0},               // 0: ROS3 Rosenbrock, 1: linearly-implicit Euler extrapolation
     {"chem.generated", 1},            // compiled-in kinetics when the mechanism's fingerprint matches
     {"chem.binning", 2},              // cells launched in cost-binned order: 1 over the mesh, 2 inside 4096-cell tiles
+    {"chem.coop", 0},                 // 1: the cooperative kernel (several lanes per cell) for any S >= 4; always on above 12 species
+    {"chem.coop_lanes", 0},           // its lanes per cell: 0 by species count, or 16 / 32 / 64 (measurement)
     {"dnn.tuned_gemm", 1},            // DF-ODENet layers by the shape-tuned kernels (0: k_mlp_gemm for every layer)
     {"halo.overlap", 0},              // several ranks: solver halo exchanges on a comm stream while the interior rows run
                                       // (read per solve; DFMI_HALO_OVERLAP sets the default when the communicator is set)

@@ -281,7 +281,7 @@ int dfmi_chem_set_options(dfmi_ctx* ctx, int mode, double rtol, double atol, dou
  * Cantera's setState_TPY(T, p, Y) (Y clipped at 0 and normalised, density p W/(R T);
  * dfChemistryModel.C:755) -> field "RR" = (Y(dt) - Y) rho / dt with rho the field "rho" (the thermo
  * density, problem.rhoi; inside dfmi_time_step / dfmi_Y_process: "rho_old", the thermo density before
- * this step's rhoEqn). Field "chem_stats" [3][C] = accepted steps (-1: step limit hit), rejected steps,
+ * this step's rhoEqn). 4..64 species, at most 256 reactions. Field "chem_stats" [3][C] = accepted steps (-1: step limit hit), rejected steps,
  * the step size the integration ended with (the next solve's first step). Returns non-zero when any
  * cell hit the step limit (its RR is then not a completed integration). */
 int dfmi_chem_solve(dfmi_ctx* ctx, double dt);
@@ -294,8 +294,9 @@ int dfmi_chem_solve(dfmi_ctx* ctx, double dt);
 int dfmi_zero_d_step(dfmi_ctx* ctx, double dt, int n_steps);
 /* integrator step budget per cell and solve (default 100000); exceeding it is an error of the call */
 int dfmi_chem_set_max_steps(dfmi_ctx* ctx, int max_steps);
-/* which integrator the last solve used: 0 data-driven generic kernel, > 0 a mechanism compiled in
- * by dfmi/chem_codegen.py (1 Burke2012_s9r23, 2 ES80_H2-7-16) */
+/* which integrator the last solve used: 0 data-driven generic kernel (one cell per lane, 4..12 species), > 0 a
+ * mechanism compiled in by dfmi/chem_codegen.py (1 Burke2012_s9r23, 2 ES80_H2-7-16), -1 the cooperative kernel
+ * (several lanes per cell: 13..64 species, or any count from 4 under option chem.coop = 1; ROS3 only) */
 int dfmi_chem_info(dfmi_ctx* ctx, int* generated);
 
 /* ---- DF-ODENet surrogate (dfChemistrySolver::setConstantValue/Inference,
