@@ -61,6 +61,7 @@ int orc_thermo_correct(int from_T);
 int orc_energy_gradient();
 int orc_correct_bc(const char* field, const char* bfield, const char* ptype, int ncomp);
 int orc_conv_weights();
+int orc_grad_scalar(const char* field, const char* bfield, const char* ptype, const char* out, const char* bout);
 }
 
 struct dfmi_ctx;
@@ -95,6 +96,9 @@ struct Level {                       // AMG level: ELL [W][n] + diagonal, work v
 struct Ctx {
   int C = 0, Ctot = 0, F = 0, B = 0, P = 0, S = 0, inert = -1;
   double rdt = 0, dt = 0;   // 1 / deltaT (bound to the restatement at every call) and deltaT as given (dfmi_set_delta_t)
+  // LES (options les.*; include/dfmi.h dfmi_turbulence_correct): the model, its coefficients and whether nut belongs to
+  // them, delta and U as they stand
+  struct Les { int model = 0; double Ck = 0.094, Ce = 1.048, Cw = 0.325, Prt = 1.0, Sct = 1.0; bool valid = false, have_delta = false; } les;
   bool step_courant = false;   // option step.courant: accepted for the callers that set it; the number is always computed on demand
   bool have_sizes = false, have_topo = false, have_geom = false, have_bgeom = false;
   std::vector<int> psize, pkind, cyc_nbr, own, nei, bfc, poff, slot_patch, prim, partner, dims, inert_v;
@@ -157,6 +161,7 @@ void allocate_fields(Ctx& x) {
   alloc(x, "boundary_Y_ref", B, S);
   alloc(x, "boundary_K_ref", B, 1);
   alloc(x, "chem_stats", C, 3);
+  alloc(x, "delta", C, 1); alloc(x, "nut", C, 1); alloc(x, "boundary_nut", B, 1);   // LES
   alloc(x, "Qdot", C, 1);   // heat release -sum_i hc_i RR_i (dfChemistryModel.C:771)
   const long ns = std::max(S, 3);
   auto wk = [&](const std::string& n, long len) { x.work[n].assign(std::max(len, 1L), 0.0); };
@@ -167,6 +172,9 @@ void allocate_fields(Ctx& x) {
   for (auto n : {"lower", "upper"}) { wk(std::string("ueqn_") + n, F); wk(std::string("peqn_") + n, F); }
   wk("ueqn_source", 3 * C); wk("ueqn_internal_coeffs", 3 * B); wk("ueqn_boundary_coeffs", 3 * B);
   wk("peqn_internal_coeffs", B); wk("peqn_boundary_coeffs", B); wk("peqn_phiHbyA", F); wk("peqn_boundary_phiHbyA", B);
+  // LES: the effective fields registered in place of mu / alpha / rhoD, and grad(U) component by component
+  wk("muEff", C); wk("boundary_muEff", B); wk("alphaEff", C); wk("boundary_alphaEff", B);
+  wk("DEff", (long)S * C); wk("boundary_DEff", (long)S * B); wk("les_g", 9 * C);
   wk("conv_w", F); wk("boundary_conv_w", B);   // div(phi,Yi_h) weights (start of YEqn, reused by EEqn)
   if (!x.work.count("boundary_delta")) wk("boundary_delta", 3 * B);
   for (auto e : {"U", "Y", "E"}) if (!x.solver.count(e)) x.solver[e] = SolverCfg{20, 1e-5, 0.0, 0};   // amgxUOptions
@@ -706,8 +714,98 @@ void kinetic(Ctx& x) {
   for (long b = 0; b < B; ++b) bK[b] = 0.5 * (bU[b] * bU[b] + bU[B + b] * bU[B + b] + bU[2 * B + b] * bU[2 * B + b]);
 }
 
+// ---------------------------------------------------------------- LES eddy viscosity (include/dfmi.h)
+// nut per cell from g[3 i + j] = d_i U_j and delta: the operation sequence of the GPU kernel (fv_kernels.hip les_nut)
+double les_nut(const Ctx::Les& q, const double* g, double del) {
+  const double D00 = g[0], D11 = g[4], D22 = g[8];
+  const double D01 = 0.5 * (g[1] + g[3]), D02 = 0.5 * (g[2] + g[6]), D12 = 0.5 * (g[5] + g[7]);
+  double k;
+  if (q.model == 1) {
+    const double tr = D00 + D11 + D22, t3 = (1.0 / 3.0) * tr;
+    const double dd = ((D00 - t3) * D00 + (D11 - t3) * D11 + (D22 - t3) * D22) + 2.0 * (D01 * D01 + D02 * D02 + D12 * D12);
+    const double a = q.Ce / del, b = (2.0 / 3.0) * tr, c = 2.0 * q.Ck * del * dd;
+    const double r = (-b + std::sqrt(b * b + 4.0 * a * c)) / (2.0 * a);
+    k = r * r;
+  } else {
+    double P[9];
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) P[3 * i + j] = g[3 * i] * g[j] + g[3 * i + 1] * g[3 + j] + g[3 * i + 2] * g[6 + j];
+    const double t3 = (1.0 / 3.0) * (P[0] + P[4] + P[8]);
+    const double S00 = P[0] - t3, S11 = P[4] - t3, S22 = P[8] - t3;
+    const double S01 = 0.5 * (P[1] + P[3]), S02 = 0.5 * (P[2] + P[6]), S12 = 0.5 * (P[5] + P[7]);
+    const double mm = (S00 * S00 + S11 * S11 + S22 * S22) + 2.0 * (S01 * S01 + S02 * S02 + S12 * S12);
+    const double ss = (D00 * D00 + D11 * D11 + D22 * D22) + 2.0 * (D01 * D01 + D02 * D02 + D12 * D12);
+    const double s52 = ss * ss * std::sqrt(ss), m54 = mm * std::sqrt(std::sqrt(mm));
+    const double den = s52 + m54, cw = q.Cw * q.Cw * del / q.Ck;
+    k = (cw * cw) * (mm * mm * mm) / (den * den + 1e-15);
+  }
+  return q.Ck * del * std::sqrt(k);
+}
+
+// turbulence->correct(): grad(U) by the restatement's Gauss gradient, one component of U at a time (the same face
+// sums as its vector gradient), nut per cell, boundary_nut by nut's patch types ("calculated" when not set)
+void turbulence_correct(Ctx& x) {
+  if (!x.les.model) return;
+  CHECK(x.les.have_delta, "LES: the filter width field 'delta' is not set (dfmi_set_field)");
+  const long C = x.C, B = x.B;
+  double* G = x.w("les_g");
+  for (int j = 0; j < 3; ++j) {
+    orc_set_d("les_u", x.f("U") + j * C); orc_set_d("les_bu", x.f("boundary_U") + j * B); orc_set_d("les_gj", G + 3 * j * C);
+    orc(orc_grad_scalar("les_u", "les_bu", "ptype_U", "les_gj", nullptr), "grad(U)");
+  }
+  const double* del = x.f("delta");
+  double* nut = x.f("nut");
+#pragma omp parallel for schedule(static)
+  for (long c = 0; c < C; ++c) {
+    double g[9];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) g[3 * i + j] = G[(3 * j + i) * C + c];
+    nut[c] = les_nut(x.les, g, del[c]);
+  }
+  orc(orc_correct_bc("nut", "boundary_nut", x.ptype.count("nut") ? "ptype_nut" : "ptype_calculated", 1), "nut boundary");
+  x.les.valid = true;
+}
+
+// mut = rho nut; muEff = mut + mu; alphaEff = alpha + mut / Prt; DEff_i = rhoD_i + mut / Sct on cells and boundary slots
+void les_effective(Ctx& x) {
+  if (!x.les.model) return;
+  CHECK(x.les.valid, "LES: nut is not valid (the model, a coefficient, delta or U changed): call dfmi_turbulence_correct");
+  for (auto pre : {"", "boundary_"}) {
+    const std::string P(pre);
+    const long n = x.fields.at(P + "rho").n;
+    const double *rho = x.f(P + "rho"), *nut = x.f(P + "nut"), *mu = x.f(P + "mu"), *al = x.f(P + "alpha"), *rd = x.f(P + "rhoD");
+    double *me = x.w(P + "muEff"), *ae = x.w(P + "alphaEff"), *de = x.w(P + "DEff");
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < n; ++i) {
+      const double mut = rho[i] * nut[i], ms = mut / x.les.Sct;
+      me[i] = mut + mu[i];
+      ae[i] = al[i] + mut / x.les.Prt;
+      for (int s = 0; s < x.S; ++s) de[s * n + i] = rd[s * n + i] + ms;
+    }
+  }
+  // the terms the reference drops for simulationType != laminar (YEqn.H:101-106, EEqn.H:30-36)
+  for (auto n : {"sumYDiffError", "hDiffCorrFlux", "diffAlphaD", "phiUc"})
+    for (auto pre : {"", "boundary_"}) { Field& f = x.fields.at(std::string(pre) + n); std::fill(f.v.begin(), f.v.end(), 0.0); }
+}
+// registers LES fields under the names the restatement reads, for one assembly; the context's own come back after it
+struct LesSwap {
+  Ctx& x;
+  std::vector<std::string> names;
+  explicit LesSwap(Ctx& c) : x(c) {}
+  void set(const std::string& name, const std::string& work) {
+    if (!x.les.model) return;
+    orc_set_d(name.c_str(), x.w(work)); orc_set_d(("boundary_" + name).c_str(), x.w("boundary_" + work));
+    names.push_back(name);
+  }
+  ~LesSwap() { for (auto& n : names) { orc_set_d(n.c_str(), x.f(n)); orc_set_d(("boundary_" + n).c_str(), x.f("boundary_" + n)); } }
+};
+
 void do_U(Ctx& x) {
-  orc(orc_u_assemble(), "UEqn");
+  les_effective(x);
+  {
+    LesSwap sw(x);
+    sw.set("mu", "muEff");
+    orc(orc_u_assemble(), "UEqn");
+  }
   const long C = x.C, F = x.F, B = x.B;
   for (auto k : {"lower", "upper"}) std::memcpy(x.w(std::string("ueqn_") + k), x.w(std::string("out_") + k), F * sizeof(double));
   std::memcpy(x.w("ueqn_source"), x.w("out_source"), 3 * C * sizeof(double));
@@ -724,8 +822,9 @@ void do_U(Ctx& x) {
 void do_Y(Ctx& x) {
   if (x.mode == 1) chem_solve(x, 1.0 / x.rdt, "rho_old");   // thermo density of the step start (chem.hip)
   CHECK(x.mode != 2, "DNN chemistry is a GPU-path feature");
+  les_effective(x);
   orc(orc_conv_weights(), "div(phi,Yi_h) weights");
-  orc(orc_y_prep(), "YEqn prep");
+  if (!x.les.model) orc(orc_y_prep(), "YEqn prep");   // LES: the preparation's terms are dropped, its fields zero
   if (study("no_diffAlphaD")) {
     std::fill_n(x.f("diffAlphaD"), x.C, 0.0);
     std::fill_n(x.f("boundary_diffAlphaD"), x.B, 0.0);
@@ -738,7 +837,11 @@ void do_Y(Ctx& x) {
   scale_field(x, "boundary_diffAlphaD", x.B, study_scale("dAD"));
   scale_field(x, "hDiffCorrFlux", 3 * x.C, study_scale("hdcf"));
   scale_field(x, "boundary_hDiffCorrFlux", 3 * x.B, study_scale("hdcf"));
-  orc(orc_y_assemble(), "YEqn");
+  {
+    LesSwap sw(x);
+    sw.set("rhoD", "DEff");
+    orc(orc_y_assemble(), "YEqn");
+  }
   const long C = x.C, F = x.F, B = x.B;
   double* Y = x.f("Y");
   bool first = true;
@@ -758,7 +861,12 @@ void do_E(Ctx& x) {
   const double sd = study_scale("dpdt");   // scaled for this EEqn only (pEqn rewrites dpdt from p)
   std::vector<double> keep;
   if (sd != 1.0) { keep.assign(x.f("dpdt"), x.f("dpdt") + x.C); scale_field(x, "dpdt", x.C, sd); }
-  orc(orc_e_assemble(), "EEqn");
+  les_effective(x);
+  {
+    LesSwap sw(x);
+    sw.set("alpha", "alphaEff");
+    orc(orc_e_assemble(), "EEqn");
+  }
   if (sd != 1.0) std::copy(keep.begin(), keep.end(), x.f("dpdt"));
   solve(x, "E", x.w("out_lower"), x.w("out_upper"), x.w("out_diag"), x.w("out_source"), x.w("out_internal_coeffs"),
         x.w("out_boundary_coeffs"), "he", x.f("he"), true);
@@ -807,6 +915,7 @@ void do_p(Ctx& x) {
 }
 
 void time_step(Ctx& x, int n_corr) {
+  if (x.les.model && !x.les.valid) turbulence_correct(x);   // turbulence->validate() (dfLowMachFoam.C:207)
   pre_time_step(x);
   orc(orc_rho_eqn(), "rhoEqn");
   do_U(x);
@@ -822,6 +931,7 @@ void time_step(Ctx& x, int n_corr) {
     orc(orc_rho_eqn(), "rhoEqn");
   }
   rho_from_psi(x);
+  turbulence_correct(x);   // turbulence->correct() (dfLowMachFoam.C:508)
 }
 
 // compressibleCourantNo.H (dfLowMachFoam.C:261): sumPhi = fvc::surfaceSum(mag(phi)) / rho, CoNum = 0.5 max(sumPhi / V)
@@ -1041,11 +1151,13 @@ int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* pt) {
     Ctx& x = ctx->x;
     CHECK(x.have_bgeom, "call dfmi_init_constant_fields_boundary first");
     const std::string f(field);
-    CHECK(f == "U" || f == "p" || f == "he" || f == "K" || f == "Y" || f == "T" || f == "rho", "unknown patch-type field '" + f + "'");
+    CHECK(f == "U" || f == "p" || f == "he" || f == "K" || f == "Y" || f == "T" || f == "rho" || f == "nut", "unknown patch-type field '" + f + "'");
     for (int p = 0; p < x.P; ++p) {
       CHECK(pt[p] >= 0 && pt[p] <= 12 && pt[p] != COUPLED, "unsupported boundary condition code");
       CHECK((x.pkind[p] == 1) == (pt[p] == CYCLIC), "field type disagrees with the mesh patch kind");
       CHECK(pt[p] != WAVE || f == "p", "waveTransmissive is supported for p");
+      CHECK(f != "nut" || pt[p] == ZG || pt[p] == FV || pt[p] == CALC || pt[p] == EMPTY || pt[p] == CYCLIC || pt[p] == PROC || pt[p] == PROC_CYC,
+            "nut takes zeroGradient, fixedValue, calculated, cyclic, processor, processorCyclic or empty");
     }
     x.ptype[f].assign(pt, pt + x.P);
   });
@@ -1074,7 +1186,17 @@ int dfmi_thermo_set_coeffs(dfmi_ctx* ctx, int S, const double* W, const double* 
 int dfmi_thermo_load(dfmi_ctx*, const char*) { return guard([&] { throw Error("dfmi (CPU-A): use dfmi_thermo_set_coeffs"); }); }
 
 int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long count, int layout) {
-  return guard([&] { copy_field(ctx->x, name, const_cast<double*>(host), count, layout, true); });
+  return guard([&] {
+    Ctx& x = ctx->x;
+    const std::string n(name ? name : "");
+    CHECK(n != "nut", "field 'nut' is formed by dfmi_turbulence_correct and cannot be set");
+    if (n == "delta")
+      for (long i = 0; i < count && i < x.C; ++i)
+        CHECK(host[i] > 0 && host[i] <= 1.79769313486231570e308, "field 'delta': the filter width must be positive and finite");
+    copy_field(x, n, const_cast<double*>(host), count, layout, true);
+    if (n == "delta" || n == "U" || n == "boundary_U") x.les.valid = false;
+    if (n == "delta") x.les.have_delta = true;
+  });
 }
 int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, int layout) {
   return guard([&] { copy_field(ctx->x, name, host, count, layout, false); });
@@ -1086,6 +1208,9 @@ int dfmi_rho_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); 
 int dfmi_U_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); do_U(ctx->x); }); }
 int dfmi_Y_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); do_Y(ctx->x); }); }
 int dfmi_E_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); do_E(ctx->x); }); }
+int dfmi_turbulence_correct(dfmi_ctx* ctx) {   // turbulence->correct() (dfLowMachFoam.C:508); laminar: nothing
+  return guard([&] { CHECK(ctx, "null context"); if (!ctx->x.les.model) return; require_ready(ctx->x); turbulence_correct(ctx->x); });
+}
 int dfmi_p_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); do_p(ctx->x); }); }
 int dfmi_U_get_HbyA(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); orc(orc_u_hbya(), "HbyA"); }); }
 int dfmi_thermo_correct(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); orc(orc_thermo_correct(0), "thermo"); }); }
@@ -1133,12 +1258,37 @@ int dfmi_step_timer(dfmi_ctx*, int) { return 0; }
 int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
   return guard([&] {
     if (ctx && key && std::string(key) == "step.courant") { ctx->x.step_courant = value != 0.0; return; }
+    if (ctx && key && std::string(key).rfind("les.", 0) == 0) {
+      Ctx::Les& q = ctx->x.les;
+      const std::string k(key);
+      double* slot = k == "les.Ck" ? &q.Ck : k == "les.Ce" ? &q.Ce : k == "les.Cw" ? &q.Cw : k == "les.Prt" ? &q.Prt : k == "les.Sct" ? &q.Sct : nullptr;
+      if (k == "les.model") {
+        CHECK(value == 0.0 || value == 1.0 || value == 2.0, "les.model must be 0 (laminar), 1 (Smagorinsky) or 2 (WALE)");
+        if ((int)value != q.model) q.valid = false;
+        q.model = (int)value;
+        return;
+      }
+      CHECK(slot, "unknown option '" + k + "'");
+      CHECK(value > 0 && value <= 1.79769313486231570e308, k + " must be positive and finite");
+      if (value != *slot) q.valid = false;
+      *slot = value;
+      return;
+    }
     throw Error(std::string("dfmi (CPU-A): option '") + key + "' is not configurable here");
   });
 }
 int dfmi_get_option(dfmi_ctx* ctx, const char* key, double* value) {
   return guard([&] {
     if (ctx && key && value && std::string(key) == "step.courant") { *value = ctx->x.step_courant ? 1.0 : 0.0; return; }
+    if (ctx && key && value && std::string(key).rfind("les.", 0) == 0) {
+      const Ctx::Les& q = ctx->x.les;
+      const std::string k(key);
+      if (k == "les.model") { *value = q.model; return; }
+      const double* slot = k == "les.Ck" ? &q.Ck : k == "les.Ce" ? &q.Ce : k == "les.Cw" ? &q.Cw : k == "les.Prt" ? &q.Prt : k == "les.Sct" ? &q.Sct : nullptr;
+      CHECK(slot, "unknown option '" + k + "'");
+      *value = *slot;
+      return;
+    }
     throw Error(std::string("dfmi (CPU-A): option '") + key + "' is not configurable here");
   });
 }
@@ -1151,8 +1301,9 @@ int dfmi_correct_boundary(dfmi_ctx* ctx, const char* field) {
     require_ready(x);
     const std::string f(field);
     const int nc = f == "U" ? 3 : (f == "Y" ? x.S : 1);
-    CHECK(f == "U" || f == "Y" || f == "p" || f == "he" || f == "T" || f == "rho" || f == "K", "unsupported field '" + f + "'");
-    orc(orc_correct_bc(f.c_str(), ("boundary_" + f).c_str(), ("ptype_" + f).c_str(), nc), "correct_boundary");
+    CHECK(f == "U" || f == "Y" || f == "p" || f == "he" || f == "T" || f == "rho" || f == "K" || f == "nut", "unsupported field '" + f + "'");
+    const std::string pt = (f == "nut" && !x.ptype.count("nut")) ? "ptype_calculated" : "ptype_" + f;
+    orc(orc_correct_bc(f.c_str(), ("boundary_" + f).c_str(), pt.c_str(), nc), "correct_boundary");
   });
 }
 

@@ -84,6 +84,17 @@ void allocate_fields(Ctx& x) {
   if (!x.solver.count("p")) x.solver["p"] = SolverCfg{1000, 1e-5, 0.0, 1};   // amgxpOptions: AMG-preconditioned
 }
 
+// LES (options les.*): the filter width and the eddy viscosity dfmi_turbulence_correct forms. Allocated when the mode,
+// one of these fields or nut's patch types is first touched: a laminar context allocates what it always did, so its
+// buffers sit where they sat (the headline step is sensitive to that: profiles/les_ab.json)
+void ensure_les_fields(Ctx& x) {
+  if (x.fields.count("nut")) return;
+  DFMI_CHECK(x.have_bgeom, "call dfmi_init_constant_fields_boundary first");
+  alloc_field(x, "delta", x.C, 1, false);
+  alloc_field(x, "nut", x.C, 1, false);
+  alloc_field(x, "boundary_nut", x.B, 1, true);
+}
+
 // Build the deterministic gather topology from owner/neighbour and the boundary face cells.
 void build_boundary_topology(Ctx& x) {
   const int C = x.C, B = x.B;
@@ -485,7 +496,7 @@ int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* patch_type
     Ctx& x = ctx->x;
     DFMI_CHECK(x.have_bgeom, "call dfmi_init_constant_fields_boundary first");
     std::string f(field);
-    static const char* ok[] = {"U", "p", "he", "K", "Y", "T", "rho"};
+    static const char* ok[] = {"U", "p", "he", "K", "Y", "T", "rho", "nut"};
     DFMI_CHECK(std::find_if(std::begin(ok), std::end(ok), [&](const char* s) { return f == s; }) != std::end(ok),
                "unknown patch-type field '" + f + "'");
     for (int p = 0; p < x.P; ++p) {
@@ -498,6 +509,8 @@ int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* patch_type
                  "patch " + std::to_string(p) + ": field '" + f + "' type disagrees with the mesh patch kind");
       DFMI_CHECK(t != GRADIENT_ENERGY || f == "he", "gradientEnergy is an energy boundary condition (field 'he')");
       DFMI_CHECK(t != FIXED_ENERGY || f == "he", "fixedEnergy is an energy boundary condition (field 'he')");
+      DFMI_CHECK(f != "nut" || t == ZERO_GRADIENT || t == FIXED_VALUE || t == CALCULATED || t == EMPTY || t == CYCLIC || bc_proc(t),
+                 "patch " + std::to_string(p) + ": nut takes zeroGradient, fixedValue, calculated, cyclic, processor, processorCyclic or empty");
     }
     set_ptype(x, f, patch_type);
     DFMI_HIP(hipStreamSynchronize(x.stream));
@@ -645,25 +658,57 @@ int dfmi_thermo_load(dfmi_ctx* ctx, const char* path) {
 }
 
 int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long count, int layout) {
-  return guard([&] { ctx->x.co.fresh = false; copy_field(ctx->x, name, host, count, layout, true); });
+  return guard([&] {
+    Ctx& x = ctx->x;
+    x.co.fresh = false;
+    const std::string n(name ? name : "");
+    if (n == "delta" || n == "nut" || n == "boundary_nut") ensure_les_fields(x);
+    DFMI_CHECK(n != "nut", "field 'nut' is formed by dfmi_turbulence_correct and cannot be set (boundary_nut holds the fixed-value slots)");
+    if (n == "delta") {
+      DFMI_CHECK(count == x.C, "field 'delta': expected " + std::to_string(x.C) + " values, got " + std::to_string(count));
+      for (long i = 0; i < count; ++i)
+        DFMI_CHECK(host[i] > 0 && host[i] <= 1.79769313486231570e308, "field 'delta': the filter width must be positive and finite");
+    }
+    copy_field(x, n, host, count, layout, true);
+    // nut belongs to delta and U as they stood at the last dfmi_turbulence_correct; the dropped terms' fields are
+    // zeroed again before the next LES assembly whatever was written here
+    if (n == "delta" || n == "U" || n == "boundary_U") x.les.valid = false;
+    if (n == "delta") x.les.have_delta = true;
+    x.les.zeroed = false;
+  });
 }
 int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, int layout) {
-  return guard([&] { copy_field(ctx->x, name, host, count, layout, false); });
+  return guard([&] {
+    const std::string n(name ? name : "");
+    if (n == "delta" || n == "nut" || n == "boundary_nut") ensure_les_fields(ctx->x);
+    copy_field(ctx->x, n, host, count, layout, false);
+  });
 }
 
 int dfmi_pre_time_step(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); copy_old(ctx->x); }); }
 int dfmi_post_time_step(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); }); }
 int dfmi_rho_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); rho_process(ctx->x, false); }); }
-int dfmi_U_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); do_U(ctx->x); }); }
+int dfmi_U_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); les_effective(ctx->x); do_U(ctx->x); }); }
 int dfmi_Y_process(dfmi_ctx* ctx) {
   return guard([&] {
     require_ready(ctx->x);
     ctx->x.dnn.prepared = false;   // a compaction left by an interrupted time step belongs to an old T
+    les_effective(ctx->x);
     do_Y(ctx->x);
     if (ctx->x.chem.mode == 1) chem_check(ctx->x);   // the Y solve's polls have passed the chemistry
   });
 }
-int dfmi_E_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); do_E(ctx->x); }); }
+int dfmi_E_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); les_effective(ctx->x); do_E(ctx->x); }); }
+// turbulence->correct() (dfLowMachFoam.C:508)
+int dfmi_turbulence_correct(dfmi_ctx* ctx) {
+  return guard([&] {
+    DFMI_CHECK(ctx, "null context");
+    if (!ctx->x.les.model) return;   // laminar: nothing to form
+    require_ready(ctx->x);
+    ensure_les_fields(ctx->x);
+    turbulence_correct(ctx->x);
+  });
+}
 int dfmi_p_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); do_p(ctx->x); }); }
 int dfmi_U_get_HbyA(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); u_hbya(ctx->x); }); }
 int dfmi_thermo_correct(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); thermo_correct(ctx->x, false); }); }
@@ -685,9 +730,11 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
     } treset{x.steptimer};
     if (x.steptimer.on && x.steptimer.used == 0) x.steptimer.mark(x.stream);
     x.dnn.prepared = false;         // never reuse a compaction of an earlier (failed) step
+    if (x.les.model && !x.les.valid) { ensure_les_fields(x); turbulence_correct(x); }   // turbulence->validate() (dfLowMachFoam.C:207)
     copy_old(x);                    // preTimeStep
     if (x.chem.mode == 2) dnn_prepare(x);   // reacting cells of this step's T (read after the UEqn polls)
     rho_process(x, false);          // rhoEqn (first PIMPLE iteration)
+    les_effective(x);               // LES: muEff, alphaEff, mut / Sct from this rho (laminar: nothing)
     const bool early = n_corr > 0 && hbya_early(x);   // the first corrector's HbyA right after the U solve
     do_U_Y_E(x, early);             // UEqn, YEqn, EEqn (one rank: the chemistry and YEqn assembly beside the
                                     // UEqn, the EEqn assembly beside the Y solve)
@@ -710,6 +757,7 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
       // dfmi_rho_process keep them for callers that read rho in between.
     }
     thermo_rho_from_psi(x);         // rho = thermo.rho() (dfLowMachFoam.C:517)
+    turbulence_correct(x);          // turbulence->correct() (dfLowMachFoam.C:508) from the last corrector's U; laminar: nothing
     if (x.chem.mode == 1) chem_check(x);   // the p solves' polls have already passed the chemistry
     // compressibleCourantNo.H of the next loop pass, queued now that the step's final phi (last pEqn) and rho are
     // written: dfmi_courant_no then reads the record instead of launching (option step.courant; off: nothing added)
@@ -812,6 +860,7 @@ int dfmi_correct_boundary(dfmi_ctx* ctx, const char* field) {
     std::string f(field);
     if (f == "Y") k_bc_correct(x, "Y", x.f("Y"), x.f("boundary_Y"), x.S);
     else if (f == "U") k_bc_correct(x, "U", x.f("U"), x.f("boundary_U"), 3);
+    else if (f == "nut" && (ensure_les_fields(x), true)) k_bc_correct(x, x.stype.count("nut") ? "nut" : "calculated", x.f("nut"), x.f("boundary_nut"), 1);
     else if (f == "p" || f == "he" || f == "T" || f == "rho" || f == "K") k_bc_correct(x, f.c_str(), x.f(f), x.f("boundary_" + f), 1);
     else throw Error("dfmi_correct_boundary: unsupported field '" + f + "'");
     halo_fields(x, {f.c_str()});
@@ -895,6 +944,7 @@ int dfmi_assemble(dfmi_ctx* ctx, const char* eqn) {
     Ctx& x = ctx->x;
     require_ready(x);
     std::string e(eqn);
+    if (e == "U" || e == "Y" || e == "Y_ell" || e == "Y_ell_ref" || e == "E") les_effective(x);
     if (e == "rho") {
       if (!x.fields.count("dbg_rho_diag")) { alloc_field(x, "dbg_rho_diag", x.C, 1, false); alloc_field(x, "dbg_rho_source", x.C, 1, false); }
       rho_process(x, true);
@@ -1178,6 +1228,18 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
     const bool global = k == "amg.global_coarse" ? value != 0.0 : x.on("amg.global_coarse");
     DFMI_CHECK(!((k == "amg.smoother" || k == "amg.global_coarse") && dilu && global),
                "dfmi_set_option: amg.smoother = 1 (multicolour DILU) and amg.global_coarse = 1 exclude each other");
+    if (k.rfind("les.", 0) == 0) {
+      if (k == "les.model")
+        DFMI_CHECK(value == 0.0 || value == 1.0 || value == 2.0,
+                   "dfmi_set_option: les.model must be 0 (laminar), 1 (Smagorinsky) or 2 (WALE)");
+      else
+        DFMI_CHECK(value > 0 && value <= 1.79769313486231570e308, "dfmi_set_option: " + k + " must be positive and finite");
+      // nut belongs to the model and its coefficients (Prt and Sct enter the effective fields, formed at every
+      // assembly, but a changed coefficient invalidates all the same: one rule)
+      if (value != x.opt(key)) { x.les.valid = false; x.les.zeroed = false; }
+      if (k == "les.model") x.les.model = (int)value;
+      if (x.les.model && x.have_bgeom) ensure_les_fields(x);
+    }
     x.opts[k] = value;
   });
 }

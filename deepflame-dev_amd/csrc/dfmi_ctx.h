@@ -271,6 +271,12 @@ inline const OptDef* option_defs(int& n) {
                                       // main stream would wait for the side stream's YEqn rows (it reads what the U solve left)
     {"step.courant", 0},              // 1: dfmi_time_step ends with the Courant-number kernel and posts its record for
                                       // dfmi_courant_no (compressibleCourantNo.H, dfLowMachFoam.C:261); 0: nothing added
+    {"les.model", 0},                 // turbulence->: 0 laminar, 1 Smagorinsky, 2 WALE (LESeddyViscosity)
+    {"les.Ck", 0.094},                // nut = Ck delta sqrt(k) (both models)
+    {"les.Ce", 1.048},                // Smagorinsky
+    {"les.Cw", 0.325},                // WALE
+    {"les.Prt", 1.0},                 // alphaEff = alpha + mut / Prt (createFields.H:133)
+    {"les.Sct", 1.0},                 // DEff_i = rhoD_i + mut / Sct
   };
   n = (int)(sizeof(d) / sizeof(d[0]));
   return d;
@@ -418,6 +424,15 @@ struct Ctx {
   int hex[3] = {0, 0, 0};   // MeshView::hx/hy/hz (build_ell)
   ~Ctx();
   int n_corr = 2;
+  // LES eddy viscosity (options les.*, fv_kernels.hip turbulence_correct): the model in force (a copy of the option,
+  // read at every launch), whether the field "nut" belongs to the model, delta and U as they stand, and whether the
+  // fields the dropped terms read (sumYDiffError, hDiffCorrFlux, diffAlphaD, phiUc) have been zeroed for this mode
+  struct Les { int model = 0; bool valid = false, zeroed = false, have_delta = false; } les;
+  // what the three assemblies read as mu / alpha: the thermo's fields, or in LES mode muEff / alphaEff (les_effective)
+  double* visc(bool boundary) { return f(std::string(boundary ? "boundary_" : "") + (les.model ? "muEff" : "mu")); }
+  double* cond(bool boundary) { return f(std::string(boundary ? "boundary_" : "") + (les.model ? "alphaEff" : "alpha")); }
+  // mut / Sct, which the species kernels add where they read rhoD (nullptr: laminar)
+  double* mut_sct(bool boundary) { return les.model ? f(boundary ? "boundary_mutSct" : "mutSct") : nullptr; }
 
   MeshView view() const {
     MeshView m;
@@ -449,7 +464,7 @@ struct Ctx {
   const double* sch_w(int i) {
     static const char* names[8] = {"conv_w", "boundary_conv_w", "K_w", "boundary_K_w", "cubic_flux",
                                    "boundary_cubic_flux", "U_w", "boundary_U_w"};
-    const bool on = i < 2 ? sch.yh != SCH_UPWIND : i < 4 ? sch.K != SCH_LINEAR : i < 6 ? sch.hD == SCH_CUBIC
+    const bool on = i < 2 ? sch.yh != SCH_UPWIND : i < 4 ? sch.K != SCH_LINEAR : i < 6 ? sch.hD == SCH_CUBIC && !les.model
                                                                                      : sch.U == SCH_LLV;
     if (!on) return nullptr;
     auto it = fields.find(names[i]);
@@ -521,6 +536,13 @@ void e_assemble_back(Ctx& x);    // boundary energy gradient, he's boundary valu
 void e_post_solve(Ctx& x);
 void conv_weights(Ctx& x);   // div(phi,Yi_h) weights (start of YEqn; EEqn reuses them)
 void copy_old(Ctx& x);
+// LES (options les.*): turbulence->correct() -- nut from grad(U) and delta, boundary_nut by nut's patch types, the
+// processor slots' neighbour half through the halo; then Ctx::les.valid. Laminar: nothing.
+void turbulence_correct(Ctx& x);
+// mut = rho nut; muEff = mut + mu; alphaEff = alpha + mut / Prt; mutSct = mut / Sct, on cells and on every boundary
+// slot from the slot's own values, from the fields as they stand (after the rhoEqn, before the three assemblies);
+// the first call in LES mode also zeroes the fields of the dropped terms. Throws when nut is not valid.
+void les_effective(Ctx& x);
 void courant_post(Ctx& x);   // queues the Courant-number reduction and its record (Ctx::co), no synchronisation
 void zero_d_step(Ctx& x, double dt);   // df0DFoam loop body for every cell
 void thermo_rho_from_psi(Ctx& x);

@@ -728,12 +728,11 @@ __device__ __forceinline__ void dev2T(double sc, const double* v, double* o) {
   o[6] = sc * v[2]; o[7] = sc * v[5]; o[8] = sc * (v[8] - tr);
 }
 
+// g[3 i + j] = d_i U_j at cell c: the Gauss linear gradient (fvc_grad_vector), faces in sequential order, then the
+// cell's boundary slots, / V -- the oracle's out_gradU (k_u_grad and the LES kernel k_les_nut share it)
 template <int WT>
-__global__ void __launch_bounds__(TPB) DFMI_WAVES(6) k_u_grad(MeshView m, const int8_t* __restrict__ ty, const double* __restrict__ U,
-                         const double* __restrict__ bU, const double* __restrict__ mu, const double* __restrict__ bmu,
-                         double* __restrict__ T, double* __restrict__ bT, double* __restrict__ gout) {
-  const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
-  if (c >= m.C) return;
+__device__ __forceinline__ void grad_u_cell(const MeshView& m, const int8_t* __restrict__ ty, const double* __restrict__ U,
+                                            const double* __restrict__ bU, int c, double (&g)[9]) {
   const long C = m.C, F = m.F, B = m.B;
   double s[9];
 #pragma unroll
@@ -764,9 +763,19 @@ __global__ void __launch_bounds__(TPB) DFMI_WAVES(6) k_u_grad(MeshView m, const 
       for (int j = 0; j < 3; ++j) s[i * 3 + j] += m.bSf[i * B + b] * uf[j];
   });
   const double vol = m.V[c];
-  double g[9], o[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) g[k] = s[k] / vol;
+}
+
+template <int WT>
+__global__ void __launch_bounds__(TPB) DFMI_WAVES(6) k_u_grad(MeshView m, const int8_t* __restrict__ ty, const double* __restrict__ U,
+                         const double* __restrict__ bU, const double* __restrict__ mu, const double* __restrict__ bmu,
+                         double* __restrict__ T, double* __restrict__ bT, double* __restrict__ gout) {
+  const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
+  if (c >= m.C) return;
+  const long C = m.C, B = m.B;
+  double g[9], o[9];
+  grad_u_cell<WT>(m, ty, U, bU, c, g);
   if (gout) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) gout[k * C + c] = g[k];
@@ -790,6 +799,68 @@ __global__ void __launch_bounds__(TPB) DFMI_WAVES(6) k_u_grad(MeshView m, const 
 #pragma unroll
     for (int k = 0; k < 9; ++k) bT[k * B + b] = bo[k];
   });
+}
+
+// ------------------------------------------------------------------ LES eddy viscosity (turbulence->correct())
+// OpenFOAM-7's LESeddyViscosity family per cell, from g = grad(U) (grad_u_cell: bitwise the UEqn's gradient), D = symm(g)
+// and the filter width delta:
+//   Smagorinsky (the formula of the reference's unused kernel, dfUEqn.cu:316-341): a = Ce / delta, b = (2/3) tr D,
+//     c = 2 Ck delta (dev(D) && D), k = ((-b + sqrt(b^2 + 4 a c)) / (2 a))^2
+//   WALE: Sd = dev(symm(g . g)), m = Sd && Sd, s = D && D,
+//     k = (Cw^2 delta / Ck)^2 m^3 / ((s^(5/2) + m^(5/4))^2 + 1e-15)
+//   nut = Ck delta sqrt(k)
+// The powers are products and square roots (s^(5/2) = s s sqrt(s), m^(5/4) = m sqrt(sqrt(m))): no pow().
+struct LesCoef { int model; double Ck, Ce, Cw; };
+__device__ __forceinline__ double les_nut(const LesCoef& q, const double (&g)[9], double del) {
+  const double D00 = g[0], D11 = g[4], D22 = g[8];
+  const double D01 = 0.5 * (g[1] + g[3]), D02 = 0.5 * (g[2] + g[6]), D12 = 0.5 * (g[5] + g[7]);
+  double k;
+  if (q.model == 1) {
+    const double tr = D00 + D11 + D22, t3 = (1.0 / 3.0) * tr;
+    const double dd = ((D00 - t3) * D00 + (D11 - t3) * D11 + (D22 - t3) * D22) + 2.0 * (D01 * D01 + D02 * D02 + D12 * D12);
+    const double a = q.Ce / del, b = (2.0 / 3.0) * tr, c = 2.0 * q.Ck * del * dd;
+    const double r = (-b + sqrt(b * b + 4.0 * a * c)) / (2.0 * a);
+    k = r * r;
+  } else {
+    double P[9];   // g . g
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) P[3 * i + j] = g[3 * i] * g[j] + g[3 * i + 1] * g[3 + j] + g[3 * i + 2] * g[6 + j];
+    const double t3 = (1.0 / 3.0) * (P[0] + P[4] + P[8]);
+    const double S00 = P[0] - t3, S11 = P[4] - t3, S22 = P[8] - t3;
+    const double S01 = 0.5 * (P[1] + P[3]), S02 = 0.5 * (P[2] + P[6]), S12 = 0.5 * (P[5] + P[7]);
+    const double mm = (S00 * S00 + S11 * S11 + S22 * S22) + 2.0 * (S01 * S01 + S02 * S02 + S12 * S12);
+    const double ss = (D00 * D00 + D11 * D11 + D22 * D22) + 2.0 * (D01 * D01 + D02 * D02 + D12 * D12);
+    const double s52 = ss * ss * sqrt(ss), m54 = mm * sqrt(sqrt(mm));
+    const double den = s52 + m54, cw = q.Cw * q.Cw * del / q.Ck;
+    k = (cw * cw) * (mm * mm * mm) / (den * den + 1e-15);
+  }
+  return q.Ck * del * sqrt(k);
+}
+// One thread per cell, k_u_grad's gather (U of the face neighbours, Sf and w of the cell's faces; the tensor in
+// registers, no atomics) and 8 B out.
+template <int WT>
+__global__ void __launch_bounds__(TPB) k_les_nut(MeshView m, const int8_t* __restrict__ ty, const double* __restrict__ U,
+                                                 const double* __restrict__ bU, const double* __restrict__ delta,
+                                                 LesCoef q, double* __restrict__ nut) {
+  const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
+  if (c >= m.C) return;
+  double g[9];
+  grad_u_cell<WT>(m, ty, U, bU, c, g);
+  nut[c] = les_nut(q, g, delta[c]);
+}
+// mut = rho nut; muEff = mut + mu; alphaEff = alpha + mut / Prt; mutSct = mut / Sct (in this order, no contraction),
+// over n cells or n boundary slots (each slot from its own boundary values)
+__global__ void k_les_effective(long n, const double* __restrict__ rho, const double* __restrict__ nut,
+                                const double* __restrict__ mu, const double* __restrict__ alpha, double Prt, double Sct,
+                                double* __restrict__ muEff, double* __restrict__ alphaEff, double* __restrict__ mutSct) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double mut = rho[i] * nut[i];
+  muEff[i] = mut + mu[i];
+  alphaEff[i] = alpha[i] + mut / Prt;
+  mutSct[i] = mut / Sct;
 }
 
 // UEqn matrix (UEqn.H:3-20): ddt(rho,U) + div(phi,U) - laplacian(mu,U) - div(mu dev2 T(gradU)),
@@ -1434,14 +1505,25 @@ __global__ void k_phiuc_slot(MeshView m, const int8_t* __restrict__ tyY, const d
 
 // Y species matrices, all non-inert species in one pass (dfYEqn.cu:571-638 fused and batched):
 // fvm::ddt(rho,Yi) + div(phi,Yi) + div(phiUc,Yi) == laplacian(rhoD_i,Yi) + RR_i
-template <int S, int WT>
+// LES (the launchers' les.model != 0): DEff_i = rhoD_i + mut / Sct wherever rhoD is read, and no phiUc term. A separate
+// instantiation whose extra arguments (mut / Sct on cells and slots) exist only there, so the laminar kernels keep
+// their arguments, code and registers (profiles/les_resource_usage.md)
+template <bool LES> struct LesDiff {};
+template <> struct LesDiff<true> { const double *mS, *bmS; };
+// the slot's correction-velocity flux: absent in LES mode
+template <bool LES> __device__ __forceinline__ double bpu(const double* __restrict__ bphiUc, int b) {
+  if constexpr (LES) return 0.0;
+  else return bphiUc[b];
+}
+template <int S, int WT, bool LES = false>
 __global__ void __launch_bounds__(TPB) k_y_assemble(MeshView m, const int8_t* __restrict__ tyY, int inert,
     const double* __restrict__ Y, const double* __restrict__ bY, const double* __restrict__ rhoD,
     const double* __restrict__ brhoD, const double* __restrict__ RR, const double* __restrict__ rho,
     const double* __restrict__ rho_old, const double* __restrict__ phi, const double* __restrict__ bphi,
     const double* __restrict__ phiUc, const double* __restrict__ bphiUc, double* __restrict__ lower,
     double* __restrict__ upper, double* __restrict__ diag, double* __restrict__ src, double* __restrict__ ic,
-    double* __restrict__ bc, MixBC mxY, const double* __restrict__ wY, const double* __restrict__ bwY) {
+    double* __restrict__ bc, MixBC mxY, const double* __restrict__ wY, const double* __restrict__ bwY,
+    LesDiff<LES> ld) {
   const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
   if (c >= m.C) return;
   const long C = m.C, F = m.F, B = m.B;
@@ -1449,8 +1531,15 @@ __global__ void __launch_bounds__(TPB) k_y_assemble(MeshView m, const int8_t* __
   double dL[S], rc[S];
 #pragma unroll
   for (int s = 0; s < S; ++s) { dL[s] = 0.0; rc[s] = rhoD[s * C + c]; }
+  if constexpr (LES) {   // LES: DEff_i = rhoD_i + mut / Sct wherever rhoD is read
+    const double mc = ld.mS[c];
+#pragma unroll
+    for (int s = 0; s < S; ++s) rc[s] = rc[s] + mc;
+  }
   each_face<WT>(m, c, [&](int f, int o2, bool own) {
-    const double ph = phi[f], pu = phiUc[f];
+    const double ph = phi[f], pu = LES ? 0.0 : phiUc[f];   // LES: no correction-velocity convection (YEqn.H:101-106)
+    double mn = 0.0;
+    if constexpr (LES) mn = ld.mS[o2];
     const double wu = wY ? wY[f] : (ph >= 0 ? 1.0 : 0.0);
     const double L1 = -wu * ph, U1 = L1 + ph;
     const double L2 = -wu * pu, U2 = L2 + pu;
@@ -1460,7 +1549,7 @@ __global__ void __launch_bounds__(TPB) k_y_assemble(MeshView m, const int8_t* __
 #pragma unroll
     for (int s = 0; s < S; ++s) {
       if (s == inert) continue;
-      const double rn = rhoD[s * C + o2];
+      const double rn = LES ? rhoD[s * C + o2] + mn : rhoD[s * C + o2];
       const double UL = dcf * ((own ? interp_f(w, rc[s], rn) : interp_f(w, rn, rc[s])) * ms);
       dL[s] -= UL;
       if (own) { lower[s * F + f] = Ls - UL; upper[s * F + f] = Us - UL; }
@@ -1482,10 +1571,15 @@ __global__ void __launch_bounds__(TPB) k_y_assemble(MeshView m, const int8_t* __
       if (s == inert) continue;
       const BCoef qc = bcoef_f(t, bY[s * B + b], wu, m.bdc[b], mxY, b, B, s);
       const BCoef ql = bcoef_f(t, bY[s * B + b], m.bw[b], m.bdc[b], mxY, b, B, s);
-      const double gam = bc_coupled(t) ? interp_b(m.bw[b], rhoD[s * C + c], nbrv(m, rhoD + s * C, brhoD + s * B, b)) : brhoD[s * B + b];
+      double gam;
+      if constexpr (LES) {
+        const int pn = m.partner[b];
+        gam = bc_coupled(t) ? interp_b(m.bw[b], rhoD[s * C + c] + ld.mS[c], pn >= 0 ? rhoD[s * C + pn] + ld.mS[pn] : brhoD[s * B + b] + ld.bmS[b])
+                 : brhoD[s * B + b] + ld.bmS[b];
+      } else gam = bc_coupled(t) ? interp_b(m.bw[b], rhoD[s * C + c], nbrv(m, rhoD + s * C, brhoD + s * B, b)) : brhoD[s * B + b];
       const double pG = gam * m.bmagSf[b];
-      ic[s * B + b] = (bphi[b] * qc.vic + bphiUc[b] * qc.vic) - pG * ql.gic;
-      bc[s * B + b] = (-bphi[b] * qc.vbc + -bphiUc[b] * qc.vbc) - (-pG * ql.gbc);
+      ic[s * B + b] = (bphi[b] * qc.vic + bpu<LES>(bphiUc, b) * qc.vic) - pG * ql.gic;
+      bc[s * B + b] = (-bphi[b] * qc.vbc + -bpu<LES>(bphiUc, b) * qc.vbc) - (-pG * ql.gbc);
     }
   });
 }
@@ -1495,14 +1589,14 @@ __global__ void __launch_bounds__(TPB) k_y_assemble(MeshView m, const int8_t* __
 // faces, coupled slots), dS = diag + sum internalCoeffs and rhs = source + non-coupled
 // boundaryCoeffs in slot order -- bitwise what k_ell_build makes from the LDU arrays, without writing
 // and re-reading lower/upper/internalCoeffs/boundaryCoeffs.
-template <int S, int WT>
+template <int S, int WT, bool LES = false>
 __global__ void __launch_bounds__(TPB) DFMI_WAVES(5) k_y_assemble_ell(MeshView m, const int8_t* __restrict__ tyY, int inert,
     const double* __restrict__ Y, const double* __restrict__ bY, const double* __restrict__ rhoD,
     const double* __restrict__ brhoD, const double* __restrict__ RR, const double* __restrict__ rho,
     const double* __restrict__ rho_old, const double* __restrict__ phi, const double* __restrict__ bphi,
     const double* __restrict__ phiUc, const double* __restrict__ bphiUc, int W, long Ce, double* __restrict__ val,
     double* __restrict__ dS, double* __restrict__ rhs, MixBC mxY, const double* __restrict__ wY,
-    const double* __restrict__ bwY) {
+    const double* __restrict__ bwY, LesDiff<LES> ld) {
   const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
   if (c >= m.C) return;
   const int pc = m.eopos ? m.eopos[c] : c;   // the solver row of c (even-odd layout)
@@ -1511,9 +1605,16 @@ __global__ void __launch_bounds__(TPB) DFMI_WAVES(5) k_y_assemble_ell(MeshView m
   double dL[S], rc[S];
 #pragma unroll
   for (int s = 0; s < S; ++s) { dL[s] = 0.0; rc[s] = rhoD[s * C + c]; }
+  if constexpr (LES) {   // LES: DEff_i = rhoD_i + mut / Sct wherever rhoD is read
+    const double mc = ld.mS[c];
+#pragma unroll
+    for (int s = 0; s < S; ++s) rc[s] = rc[s] + mc;
+  }
   int k = 0;
   each_face<WT>(m, c, [&](int f, int o2, bool own) {
-    const double ph = phi[f], pu = phiUc[f];
+    const double ph = phi[f], pu = LES ? 0.0 : phiUc[f];   // LES: no correction-velocity convection (YEqn.H:101-106)
+    double mn = 0.0;
+    if constexpr (LES) mn = ld.mS[o2];
     const double wu = wY ? wY[f] : (ph >= 0 ? 1.0 : 0.0);
     const double L1 = -wu * ph, U1 = L1 + ph;
     const double L2 = -wu * pu, U2 = L2 + pu;
@@ -1524,7 +1625,7 @@ __global__ void __launch_bounds__(TPB) DFMI_WAVES(5) k_y_assemble_ell(MeshView m
     for (int s = 0; s < S; ++s) {
       if (s == inert) continue;
       const int ss = s < inert ? s : s - 1;
-      const double rn = rhoD[s * C + o2];
+      const double rn = LES ? rhoD[s * C + o2] + mn : rhoD[s * C + o2];
       const double UL = dcf * ((own ? interp_f(w, rc[s], rn) : interp_f(w, rn, rc[s])) * ms);
       dL[s] -= UL;
       st_drop(&val[((long)ss * W + k) * C + pc], own ? Us - UL : Ls - UL);
@@ -1549,10 +1650,15 @@ __global__ void __launch_bounds__(TPB) DFMI_WAVES(5) k_y_assemble_ell(MeshView m
       const int ss = s < inert ? s : s - 1;
       const BCoef qc = bcoef_f(t, bY[s * B + b], wu, m.bdc[b], mxY, b, B, s);
       const BCoef ql = bcoef_f(t, bY[s * B + b], m.bw[b], m.bdc[b], mxY, b, B, s);
-      const double gam = cp ? interp_b(m.bw[b], rhoD[s * C + c], nbrv(m, rhoD + s * C, brhoD + s * B, b)) : brhoD[s * B + b];
+      double gam;
+      if constexpr (LES) {
+        const int pn = m.partner[b];
+        gam = cp ? interp_b(m.bw[b], rhoD[s * C + c] + ld.mS[c], pn >= 0 ? rhoD[s * C + pn] + ld.mS[pn] : brhoD[s * B + b] + ld.bmS[b])
+                 : brhoD[s * B + b] + ld.bmS[b];
+      } else gam = cp ? interp_b(m.bw[b], rhoD[s * C + c], nbrv(m, rhoD + s * C, brhoD + s * B, b)) : brhoD[s * B + b];
       const double pG = gam * m.bmagSf[b];
-      const double icv = (bphi[b] * qc.vic + bphiUc[b] * qc.vic) - pG * ql.gic;
-      const double bcv = (-bphi[b] * qc.vbc + -bphiUc[b] * qc.vbc) - (-pG * ql.gbc);
+      const double icv = (bphi[b] * qc.vic + bpu<LES>(bphiUc, b) * qc.vic) - pG * ql.gic;
+      const double bcv = (-bphi[b] * qc.vbc + -bpu<LES>(bphiUc, b) * qc.vbc) - (-pG * ql.gbc);
       dg[s] += icv;
       if (cp) st_drop(&val[((long)ss * W + k) * C + pc], -bcv);
       else sr[s] += bcv;
@@ -1788,14 +1894,15 @@ __global__ void __launch_bounds__(TPB) DFMI_WAVES(4) k_y_prep_gen(MeshView m, in
 }
 
 // YEqn matrices, chunked over species (LDU form: the dfmi_assemble("Y") inspection path)
-template <int CH, int WT>
+template <int CH, int WT, bool LES = false>
 __global__ void __launch_bounds__(TPB) k_y_assemble_gen(MeshView m, int S, const int8_t* __restrict__ tyY, int inert,
     const double* __restrict__ Y, const double* __restrict__ bY, const double* __restrict__ rhoD,
     const double* __restrict__ brhoD, const double* __restrict__ RR, const double* __restrict__ rho,
     const double* __restrict__ rho_old, const double* __restrict__ phi, const double* __restrict__ bphi,
     const double* __restrict__ phiUc, const double* __restrict__ bphiUc, double* __restrict__ lower,
     double* __restrict__ upper, double* __restrict__ diag, double* __restrict__ src, double* __restrict__ ic,
-    double* __restrict__ bc, MixBC mxY, const double* __restrict__ wY, const double* __restrict__ bwY) {
+    double* __restrict__ bc, MixBC mxY, const double* __restrict__ wY, const double* __restrict__ bwY,
+    LesDiff<LES> ld) {
   const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
   if (c >= m.C) return;
   const long C = m.C, F = m.F, B = m.B;
@@ -1805,8 +1912,15 @@ __global__ void __launch_bounds__(TPB) k_y_assemble_gen(MeshView m, int S, const
     double dL[CH], rc[CH];
 #pragma unroll
     for (int j = 0; j < CH; ++j) { dL[j] = 0.0; rc[j] = s0 + j < S ? rhoD[(s0 + j) * C + c] : 0.0; }
+    if constexpr (LES) {   // LES: DEff_i = rhoD_i + mut / Sct wherever rhoD is read
+      const double mc = ld.mS[c];
+#pragma unroll
+      for (int j = 0; j < CH; ++j) rc[j] = rc[j] + mc;
+    }
     each_face<WT>(m, c, [&](int f, int o2, bool own) {
-      const double ph = phi[f], pu = phiUc[f];
+      const double ph = phi[f], pu = LES ? 0.0 : phiUc[f];   // LES: no correction-velocity convection (YEqn.H:101-106)
+      double mn = 0.0;
+      if constexpr (LES) mn = ld.mS[o2];
       const double wu = wY ? wY[f] : (ph >= 0 ? 1.0 : 0.0);
       const double L1 = -wu * ph, U1 = L1 + ph;
       const double L2 = -wu * pu, U2 = L2 + pu;
@@ -1818,7 +1932,7 @@ __global__ void __launch_bounds__(TPB) k_y_assemble_gen(MeshView m, int S, const
         const int s = s0 + j;
         if (s >= S) break;
         if (s == inert) continue;
-        const double rn = rhoD[s * C + o2];
+        const double rn = LES ? rhoD[s * C + o2] + mn : rhoD[s * C + o2];
         const double UL = dcf * ((own ? interp_f(w, rc[j], rn) : interp_f(w, rn, rc[j])) * ms);
         dL[j] -= UL;
         if (own) { lower[s * F + f] = Ls - UL; upper[s * F + f] = Us - UL; }
@@ -1843,10 +1957,15 @@ __global__ void __launch_bounds__(TPB) k_y_assemble_gen(MeshView m, int S, const
         if (s == inert) continue;
         const BCoef qc = bcoef_f(t, bY[s * B + b], wu, m.bdc[b], mxY, b, B, s);
         const BCoef ql = bcoef_f(t, bY[s * B + b], m.bw[b], m.bdc[b], mxY, b, B, s);
-        const double gam = bc_coupled(t) ? interp_b(m.bw[b], rhoD[s * C + c], nbrv(m, rhoD + s * C, brhoD + s * B, b)) : brhoD[s * B + b];
+        double gam;
+        if constexpr (LES) {
+          const int pn = m.partner[b];
+          gam = bc_coupled(t) ? interp_b(m.bw[b], rhoD[s * C + c] + ld.mS[c], pn >= 0 ? rhoD[s * C + pn] + ld.mS[pn] : brhoD[s * B + b] + ld.bmS[b])
+                   : brhoD[s * B + b] + ld.bmS[b];
+        } else gam = bc_coupled(t) ? interp_b(m.bw[b], rhoD[s * C + c], nbrv(m, rhoD + s * C, brhoD + s * B, b)) : brhoD[s * B + b];
         const double pG = gam * m.bmagSf[b];
-        ic[s * B + b] = (bphi[b] * qc.vic + bphiUc[b] * qc.vic) - pG * ql.gic;
-        bc[s * B + b] = (-bphi[b] * qc.vbc + -bphiUc[b] * qc.vbc) - (-pG * ql.gbc);
+        ic[s * B + b] = (bphi[b] * qc.vic + bpu<LES>(bphiUc, b) * qc.vic) - pG * ql.gic;
+        bc[s * B + b] = (-bphi[b] * qc.vbc + -bpu<LES>(bphiUc, b) * qc.vbc) - (-pG * ql.gbc);
       }
     });
   }
@@ -1855,14 +1974,14 @@ __global__ void __launch_bounds__(TPB) k_y_assemble_gen(MeshView m, int S, const
 // YEqn in the solver's ELL rows, chunked over species (production path for S > 16)
 // One launch covers the species [s_lo, s_hi) (the species are independent here; split for L2 locality of the
 // neighbour rhoD gathers, as k_y_prep_gen)
-template <int CH, int WT>
+template <int CH, int WT, bool LES = false>
 __global__ void __launch_bounds__(TPB) k_y_assemble_ell_gen(MeshView m, int s_lo, int S, const int8_t* __restrict__ tyY, int inert,
     const double* __restrict__ Y, const double* __restrict__ bY, const double* __restrict__ rhoD,
     const double* __restrict__ brhoD, const double* __restrict__ RR, const double* __restrict__ rho,
     const double* __restrict__ rho_old, const double* __restrict__ phi, const double* __restrict__ bphi,
     const double* __restrict__ phiUc, const double* __restrict__ bphiUc, int W, long Ce, double* __restrict__ val,
     double* __restrict__ dS, double* __restrict__ rhs, MixBC mxY, const double* __restrict__ wY,
-    const double* __restrict__ bwY) {
+    const double* __restrict__ bwY, LesDiff<LES> ld) {
   const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
   if (c >= m.C) return;
   const int pc = m.eopos ? m.eopos[c] : c;   // the solver row of c (even-odd layout)
@@ -1873,9 +1992,16 @@ __global__ void __launch_bounds__(TPB) k_y_assemble_ell_gen(MeshView m, int s_lo
     double dL[CH], rc[CH];
 #pragma unroll
     for (int j = 0; j < CH; ++j) { dL[j] = 0.0; rc[j] = s0 + j < S ? rhoD[(s0 + j) * C + c] : 0.0; }
+    if constexpr (LES) {   // LES: DEff_i = rhoD_i + mut / Sct wherever rhoD is read
+      const double mc = ld.mS[c];
+#pragma unroll
+      for (int j = 0; j < CH; ++j) rc[j] = rc[j] + mc;
+    }
     int k = 0;
     each_face<WT>(m, c, [&](int f, int o2, bool own) {
-      const double ph = phi[f], pu = phiUc[f];
+      const double ph = phi[f], pu = LES ? 0.0 : phiUc[f];   // LES: no correction-velocity convection (YEqn.H:101-106)
+      double mn = 0.0;
+      if constexpr (LES) mn = ld.mS[o2];
       const double wu = wY ? wY[f] : (ph >= 0 ? 1.0 : 0.0);
       const double L1 = -wu * ph, U1 = L1 + ph;
       const double L2 = -wu * pu, U2 = L2 + pu;
@@ -1888,7 +2014,7 @@ __global__ void __launch_bounds__(TPB) k_y_assemble_ell_gen(MeshView m, int s_lo
         if (s >= S) break;
         if (s == inert) continue;
         const int ss = s < inert ? s : s - 1;
-        const double rn = rhoD[s * C + o2];
+        const double rn = LES ? rhoD[s * C + o2] + mn : rhoD[s * C + o2];
         const double UL = dcf * ((own ? interp_f(w, rc[j], rn) : interp_f(w, rn, rc[j])) * ms);
         dL[j] -= UL;
         val[((long)ss * W + k) * C + pc] = own ? Us - UL : Ls - UL;
@@ -1915,10 +2041,15 @@ __global__ void __launch_bounds__(TPB) k_y_assemble_ell_gen(MeshView m, int s_lo
         const int ss = s < inert ? s : s - 1;
         const BCoef qc = bcoef_f(t, bY[s * B + b], wu, m.bdc[b], mxY, b, B, s);
         const BCoef ql = bcoef_f(t, bY[s * B + b], m.bw[b], m.bdc[b], mxY, b, B, s);
-        const double gam = cp ? interp_b(m.bw[b], rhoD[s * C + c], nbrv(m, rhoD + s * C, brhoD + s * B, b)) : brhoD[s * B + b];
+        double gam;
+        if constexpr (LES) {
+          const int pn = m.partner[b];
+          gam = cp ? interp_b(m.bw[b], rhoD[s * C + c] + ld.mS[c], pn >= 0 ? rhoD[s * C + pn] + ld.mS[pn] : brhoD[s * B + b] + ld.bmS[b])
+                   : brhoD[s * B + b] + ld.bmS[b];
+        } else gam = cp ? interp_b(m.bw[b], rhoD[s * C + c], nbrv(m, rhoD + s * C, brhoD + s * B, b)) : brhoD[s * B + b];
         const double pG = gam * m.bmagSf[b];
-        const double icv = (bphi[b] * qc.vic + bphiUc[b] * qc.vic) - pG * ql.gic;
-        const double bcv = (-bphi[b] * qc.vbc + -bphiUc[b] * qc.vbc) - (-pG * ql.gbc);
+        const double icv = (bphi[b] * qc.vic + bpu<LES>(bphiUc, b) * qc.vic) - pG * ql.gic;
+        const double bcv = (-bphi[b] * qc.vbc + -bpu<LES>(bphiUc, b) * qc.vbc) - (-pG * ql.gbc);
         dg[j] += icv;
         if (cp) val[((long)ss * W + k) * C + pc] = -bcv;
         else sr[j] += bcv;
@@ -2063,6 +2194,10 @@ template <template <int> class K, class... A> void dispatch_S(int S, dim3 g, dim
   do { KScope _ks(x, name); if ((n) > 0) hipLaunchKernelGGL(kernel, dim3(blocks_for((n), TPB)), dim3(TPB), 0, x.stream, __VA_ARGS__); \
        DFMI_HIP(hipGetLastError()); } while (0)
 
+template <bool L> LesDiff<L> les_diff(Ctx& x) {
+  if constexpr (L) return {x.mut_sct(false), x.mut_sct(true)};
+  else return {};
+}
 // kernels templated on the ELL width: the unrolled path for hex meshes (W = 6), the CSR walk otherwise
 // (option fv.csr_walk forces the CSR walk everywhere: A/B measurement and parity of both paths)
 bool face_rows(const Ctx& x) { return x.ell.W == 6 && !x.on("fv.csr_walk"); }
@@ -2075,6 +2210,17 @@ bool face_hex(const Ctx& x) { return x.hex[0] > 0 && x.on("fv.hex_walk") && !x.o
 // y_prep 9.5 against 17.5 ms by the face rows and 8.61 against 8.71 ms by the computed hex walk (its 179 VGPRs:
 // two waves per SIMD), y_assemble_ell 4.5 / 4.43 against 6.1 / 5.84 ms (round 4, scripts/c4_ab.sh)
 #define LAUNCH_SWG(kern, NS, n, ...) LAUNCH((kern<NS, 0>), n, __VA_ARGS__)
+// the YEqn assembly kernels, whose LES form (Ctx::les.model != 0) is an instantiation of its own
+// (the kernels' last argument, LesDiff<L>, is appended here)
+#define LAUNCH_SWGL(kern, NS, n, ...) \
+  do { if (x.les.model) LAUNCH((kern<NS, 0, true>), n, __VA_ARGS__, les_diff<true>(x)); \
+       else LAUNCH((kern<NS, 0, false>), n, __VA_ARGS__, les_diff<false>(x)); } while (0)
+#define LAUNCH_SW_(kern, NS, L, n, ...) \
+  do { if (face_hex(x)) LAUNCH((kern<NS, -1, L>), n, __VA_ARGS__, les_diff<L>(x)); \
+       else if (face_rows(x)) LAUNCH((kern<NS, 6, L>), n, __VA_ARGS__, les_diff<L>(x)); \
+       else LAUNCH((kern<NS, 0, L>), n, __VA_ARGS__, les_diff<L>(x)); } while (0)
+#define LAUNCH_SWL(kern, NS, n, ...) \
+  do { if (x.les.model) LAUNCH_SW_(kern, NS, true, n, __VA_ARGS__); else LAUNCH_SW_(kern, NS, false, n, __VA_ARGS__); } while (0)
 #define LAUNCH_SW(kern, NS, n, ...) \
   do { if (face_hex(x)) LAUNCH((kern<NS, -1>), n, __VA_ARGS__); else if (face_rows(x)) LAUNCH((kern<NS, 6>), n, __VA_ARGS__); \
        else LAUNCH((kern<NS, 0>), n, __VA_ARGS__); } while (0)
@@ -2166,7 +2312,7 @@ void u_assemble(Ctx& x) {
   Matrix& A = x.mU;
   const bool llv = x.sch.U == SCH_LLV;
   double* gout = llv ? scheme_buf(x, "gradU", x.C, 9) : x.fields.count("dbg_gradU") ? x.f("dbg_gradU") : nullptr;
-  LAUNCH_W(k_u_grad, x.C, x.view(), x.st("U"), x.f("U"), x.f("boundary_U"), x.f("mu"), x.f("boundary_mu"),
+  LAUNCH_W(k_u_grad, x.C, x.view(), x.st("U"), x.f("U"), x.f("boundary_U"), x.visc(false), x.visc(true),
          x.f("tauU"), x.f("boundary_tauU"), gout);
   halo_fields(x, {"tauU"});   // fvc_grad_vector_correctBC_processor (dfMatrixOpBase.cu:1366-1389)
   if (llv) {   // div(phi,U) limitedLinearV weights from this grad(U)
@@ -2182,7 +2328,7 @@ void u_assemble(Ctx& x) {
     LAUNCH(k_llv_w_slot, x.B, x.view(), x.st("U"), twoByk, x.f("boundary_phi"), x.f("U"), gout, bw);
   }
   LAUNCH_W(k_u_assemble, x.C, x.view(), x.st("U"), x.st("p"), x.f("rho"), x.f("rho_old"), x.f("U_old"),
-           x.f("boundary_U"), x.f("phi"), x.f("boundary_phi"), x.f("mu"), x.f("boundary_mu"), x.f("p"),
+           x.f("boundary_U"), x.f("phi"), x.f("boundary_phi"), x.visc(false), x.visc(true), x.f("p"),
            x.f("boundary_p"), x.f("tauU"), x.f("boundary_tauU"), A.lower.p, A.upper.p, A.diag.p, A.source.p,
            A.source_solve.p, A.ic.p, A.bc.p, x.f("rAU"), mixbc(x, "U"), x.sch_w(6), x.sch_w(7));
   k_bc_correct(x, "extrapolated", x.f("rAU"), x.f("boundary_rAU"), 1);
@@ -2204,6 +2350,36 @@ void u_hbya(Ctx& x) {
   LAUNCH(k_hbya_scale_cells, x.C, x.C, x.f("rAU"), x.f("HbyA"));
   LAUNCH(k_hbya_scale_slots, x.B, x.B, x.st("U"), x.f("boundary_rAU"), x.f("boundary_U"), x.f("boundary_HbyA"));
   halo_fields(x, {"HbyA"});
+}
+
+// turbulence->correct() (dfLowMachFoam.C:508): nut from U / boundary_U as they stand, boundary_nut by
+// nut.correctBoundaryConditions() with nut's patch types (not set: "calculated", OpenFOAM's default for nut -- the
+// stored values are kept), the processor slots' neighbour half through the halo
+void turbulence_correct(Ctx& x) {
+  if (!x.les.model) return;
+  DFMI_CHECK(x.les.have_delta, "LES: the filter width field 'delta' is not set (dfmi_set_field)");
+  const LesCoef q{x.les.model, x.opt("les.Ck"), x.opt("les.Ce"), x.opt("les.Cw")};
+  LAUNCH_W(k_les_nut, x.C, x.view(), x.st("U"), x.f("U"), x.f("boundary_U"), x.f("delta"), q, x.f("nut"));
+  k_bc_correct(x, x.stype.count("nut") ? "nut" : "calculated", x.f("nut"), x.f("boundary_nut"), 1);
+  halo_fields(x, {"nut"});
+  x.les.valid = true;
+}
+
+void les_effective(Ctx& x) {
+  if (!x.les.model) return;
+  DFMI_CHECK(x.les.valid, "LES: nut is not valid (the model, a coefficient, delta or U changed): call dfmi_turbulence_correct");
+  double* cell[3] = {scheme_buf(x, "muEff", x.C, 1), scheme_buf(x, "alphaEff", x.C, 1), scheme_buf(x, "mutSct", x.C, 1)};
+  double* slot[3] = {scheme_buf(x, "boundary_muEff", x.B, 1), scheme_buf(x, "boundary_alphaEff", x.B, 1),
+                     scheme_buf(x, "boundary_mutSct", x.B, 1)};
+  if (!x.les.zeroed) {   // the dropped terms' fields read back as zeros, and the EEqn kernel reads them as such
+    for (const char* n : {"sumYDiffError", "hDiffCorrFlux", "diffAlphaD", "phiUc"})
+      for (const char* pre : {"", "boundary_"}) x.fields.at(std::string(pre) + n).buf.zero(x.stream);
+    x.les.zeroed = true;
+  }
+  const double Prt = x.opt("les.Prt"), Sct = x.opt("les.Sct");
+  LAUNCH(k_les_effective, x.C, (long)x.C, x.f("rho"), x.f("nut"), x.f("mu"), x.f("alpha"), Prt, Sct, cell[0], cell[1], cell[2]);
+  LAUNCH(k_les_effective, x.B, (long)x.B, x.f("boundary_rho"), x.f("boundary_nut"), x.f("boundary_mu"),
+         x.f("boundary_alpha"), Prt, Sct, slot[0], slot[1], slot[2]);
 }
 
 void p_assemble(Ctx& x, bool cell_pass) {
@@ -2351,7 +2527,7 @@ static void e_scheme_terms(Ctx& x) {
       LAUNCH(k_upwind_w_slot, x.B, m, x.f("boundary_phi"), bw);
     }
   }
-  if (x.sch.hD == SCH_CUBIC) {
+  if (x.sch.hD == SCH_CUBIC && !x.les.model) {   // LES: no div(hDiffCorrFlux) (EEqn.H:30-36), so no correction of it
     double* cf = scheme_buf(x, "cubic_flux", x.Fs, 1, true);
     double* bcf = scheme_buf(x, "boundary_cubic_flux", x.B, 1);
     double* g = scheme_buf(x, "gradHD", x.C, 9);
@@ -2369,6 +2545,9 @@ static void e_scheme_terms(Ctx& x) {
 
 void y_prep(Ctx& x, bool weights) {
   if (weights) conv_weights(x);   // div(phi,Yi_h) weights of this step (before Y changes)
+  // LES (simulationType != laminar): the reference drops fvmDiv(phiUc, Yi), diffAlphaD and div(hDiffCorrFlux)
+  // (YEqn.H:101-106, EEqn.H:30-36) -- everything below; their fields stay zero (les_effective)
+  if (x.les.model) return;
   MeshView m = x.view();
   double* gout = x.fields.count("dbg_gradY") ? x.f("dbg_gradY") : nullptr;
 // (k_y_prep: the CSR walk measured faster than the gather rows -- 667 vs 848 us on the 2M box; its
@@ -2419,11 +2598,11 @@ void y_prep(Ctx& x, bool weights) {
 void y_assemble(Ctx& x) {
   Matrix& A = x.mY;
   MeshView m = x.view();
-#define CALL(NS) LAUNCH_SW(k_y_assemble, NS, x.C, m, x.st("Y"), x.inert, x.f("Y"), x.f("boundary_Y"), x.f("rhoD"),   \
+#define CALL(NS) LAUNCH_SWL(k_y_assemble, NS, x.C, m, x.st("Y"), x.inert, x.f("Y"), x.f("boundary_Y"), x.f("rhoD"),   \
                         x.f("boundary_rhoD"), x.f("RR"), x.f("rho"), x.f("rho_old"), x.f("phi"), x.f("boundary_phi"), \
                         x.f("phiUc"), x.f("boundary_phiUc"), A.lower.p, A.upper.p, A.diag.p, A.source.p, A.ic.p, A.bc.p, mixbc(x, "Y"), x.sch_w(0), x.sch_w(1))
   DFMI_SWITCH_S(x.S, CALL,
-                LAUNCH_SWG(k_y_assemble_gen, YCH, x.C, m, x.S, x.st("Y"), x.inert, x.f("Y"), x.f("boundary_Y"), x.f("rhoD"),
+                LAUNCH_SWGL(k_y_assemble_gen, YCH, x.C, m, x.S, x.st("Y"), x.inert, x.f("Y"), x.f("boundary_Y"), x.f("rhoD"),
                        x.f("boundary_rhoD"), x.f("RR"), x.f("rho"), x.f("rho_old"), x.f("phi"), x.f("boundary_phi"),
                        x.f("phiUc"), x.f("boundary_phiUc"), A.lower.p, A.upper.p, A.diag.p, A.source.p, A.ic.p, A.bc.p, mixbc(x, "Y"), x.sch_w(0), x.sch_w(1)))
 #undef CALL
@@ -2433,7 +2612,7 @@ void y_assemble_ell(Ctx& x, int W, long Ce, double* val, double* dS, double* rhs
   MeshView m = x.view();
   // (the z-marching tile form measured slower than this cell-parallel kernel, 961 vs 622 us, and is removed)
 #define CALL(NS)                                                                                                     \
-  LAUNCH_SW(k_y_assemble_ell, NS, x.C, m, x.st("Y"), x.inert, x.f("Y"), x.f("boundary_Y"), x.f("rhoD"),              \
+  LAUNCH_SWL(k_y_assemble_ell, NS, x.C, m, x.st("Y"), x.inert, x.f("Y"), x.f("boundary_Y"), x.f("rhoD"),              \
             x.f("boundary_rhoD"), x.f("RR"), x.f("rho"), x.f("rho_old"), x.f("phi"),                                 \
             x.f("boundary_phi"), x.f("phiUc"), x.f("boundary_phiUc"), W, Ce, val, dS, rhs, mixbc(x, "Y"), x.sch_w(0), x.sch_w(1))
   // chunked kernel: 8 species per chunk, species ranges of YASM_LCH per launch (assembly 5.98 -> 5.86 ms per step
@@ -2442,7 +2621,7 @@ void y_assemble_ell(Ctx& x, int W, long Ce, double* val, double* dS, double* rhs
   do {                                                                                                               \
     constexpr int lch = YASM_LCH / CH * CH;                                                                          \
     for (int s_lo = 0; s_lo < x.S; s_lo += lch)                                                                      \
-      LAUNCH_SWG(k_y_assemble_ell_gen, CH, x.C, m, s_lo, std::min(x.S, s_lo + lch), x.st("Y"), x.inert, x.f("Y"),    \
+      LAUNCH_SWGL(k_y_assemble_ell_gen, CH, x.C, m, s_lo, std::min(x.S, s_lo + lch), x.st("Y"), x.inert, x.f("Y"),    \
                  x.f("boundary_Y"), x.f("rhoD"), x.f("boundary_rhoD"), x.f("RR"), x.f("rho"), x.f("rho_old"), x.f("phi"), \
                  x.f("boundary_phi"), x.f("phiUc"), x.f("boundary_phiUc"), W, Ce, val, dS, rhs, mixbc(x, "Y"),       \
                  x.sch_w(0), x.sch_w(1));                                                                            \
@@ -2471,8 +2650,8 @@ void e_assemble_back(Ctx& x) {
   k_bc_correct(x, "he", x.f("he"), x.f("boundary_he"), 1);
   const double* eg = x.f("boundary_heGradient");
   LAUNCH_W(k_e_assemble, x.C, m, x.st("he"), x.st("K"), x.f("he"), x.f("boundary_he"), x.f("rho"), x.f("rho_old"),
-         x.f("K"), x.f("K_old"), x.f("boundary_K"), x.f("phi"), x.f("boundary_phi"), x.f("alpha"),
-         x.f("boundary_alpha"), x.f("hDiffCorrFlux"), x.f("boundary_hDiffCorrFlux"), x.f("dpdt"), x.f("diffAlphaD"),
+         x.f("K"), x.f("K_old"), x.f("boundary_K"), x.f("phi"), x.f("boundary_phi"), x.cond(false),
+         x.cond(true), x.f("hDiffCorrFlux"), x.f("boundary_hDiffCorrFlux"), x.f("dpdt"), x.f("diffAlphaD"),
          eg, A.lower.p, A.upper.p, A.diag.p, A.source.p, A.ic.p, A.bc.p, x.sch_w(0), x.sch_w(1), x.sch_w(2),
          x.sch_w(3), x.sch_w(4), x.sch_w(5));
 }

@@ -55,7 +55,7 @@ SIGNATURES = {
     "dfmi_set_field": [_P, C.c_char_p, _DP, C.c_long, C.c_int],
     "dfmi_get_field": [_P, C.c_char_p, _DP, C.c_long, C.c_int],
     "dfmi_pre_time_step": [_P], "dfmi_rho_process": [_P], "dfmi_U_process": [_P], "dfmi_Y_process": [_P],
-    "dfmi_E_process": [_P], "dfmi_thermo_correct": [_P], "dfmi_thermo_update_energy": [_P],
+    "dfmi_E_process": [_P], "dfmi_turbulence_correct": [_P], "dfmi_thermo_correct": [_P], "dfmi_thermo_update_energy": [_P],
     "dfmi_thermo_update_rho": [_P], "dfmi_thermo_psip0": [_P], "dfmi_thermo_correct_psip_rho": [_P],
     "dfmi_U_get_HbyA": [_P], "dfmi_p_process": [_P], "dfmi_post_time_step": [_P],
     "dfmi_time_step": [_P, C.c_int], "dfmi_sync": [_P],
@@ -436,6 +436,11 @@ class Context:
 
     def time_step(self, n_corr=2):
         self._call("dfmi_time_step", self.h, int(n_corr))
+
+    def turbulence_correct(self):
+        """nut and boundary_nut from U as it stands (include/dfmi.h dfmi_turbulence_correct: turbulence->correct(),
+        dfLowMachFoam.C:508; options les.*). Laminar (les.model = 0): nothing. Several ranks: a collective."""
+        self._call("dfmi_turbulence_correct", self.h)
 
     def courant_no(self):
         """(CoNum, meanCoNum) of the current phi, rho and step size (include/dfmi.h dfmi_courant_no:

@@ -372,6 +372,7 @@ def hex_box(nx: int, ny: int, nz: int, lengths=(6.283185307179586e-3,) * 3,
              global_offset=rank * C, n_total_cells=C * nranks)
     m.local_index = (ii, jj, kk)
     m.nodes = (xs, ys, zs)
+    m.extent = tuple(float(v) for v in lengths)   # of the whole box (dfmi.turbulence: the thickness of a 2-D case)
     m.block = (rx, ry, rz)
     m.block_dims = (lnx, lny, lnz)
     return m

@@ -221,6 +221,8 @@ def decompose(m: Mesh, part: np.ndarray) -> list:
                    global_offset=int(offset[r]), n_total_cells=int(m.n_cells))
         sub.cell_map = cells
         sub.rank = r
+        if hasattr(m, "extent"):
+            sub.extent = m.extent
         out.append(sub)
     return out
 

@@ -201,9 +201,11 @@ def read_polymesh(directory: str) -> Mesh:
             p = Patch(name, "wall", fc.astype(np.int32), sf, mag, np.ones(fc.size), 1.0 / np.linalg.norm(delta, axis=1),
                       delta=delta)
         patches.append(p)
-    return Mesh(n_cells=C, owner=owner[:Fi].astype(np.int32), neighbour=neighbour.astype(np.int32), sf=sfi,
-                mag_sf=magsf, weight=w, delta_coeffs=dcoef, volume=vol, cell_centres=cc, mesh_distance=mdist,
-                patches=patches, global_offset=0, n_total_cells=C)
+    m = Mesh(n_cells=C, owner=owner[:Fi].astype(np.int32), neighbour=neighbour.astype(np.int32), sf=sfi,
+             mag_sf=magsf, weight=w, delta_coeffs=dcoef, volume=vol, cell_centres=cc, mesh_distance=mdist,
+             patches=patches, global_offset=0, n_total_cells=C)
+    m.extent = tuple(np.ptp(np.asarray(pts, dtype=np.float64), axis=0))   # bounding box (dfmi.turbulence: 2-D thickness)
+    return m
 
 
 # ------------------------------------------------------------------ writer (single hex block)

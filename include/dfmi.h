@@ -124,7 +124,9 @@ int dfmi_set_traversal(dfmi_ctx* ctx, const int* order);
 /* ---- per-equation patch types ------------------------------------------------------------ */
 /* dfUEqn/dfYEqn/dfEEqn/dfpEqn/dfRhoEqn/dfThermo::setConstantFields (e.g. dfUEqn.cu:364-379,
  * dfEEqn.cu setConstantFields, dfThermo.cu setConstantFields). field in
- * {"U","p","he","K","Y","T","rho"}; patch_type[num_patches] */
+ * {"U","p","he","K","Y","T","rho","nut"}; patch_type[num_patches]. "nut" (LES, below) takes zeroGradient, fixedValue,
+ * calculated, cyclic, processor, processorCyclic and empty; not set, it is "calculated" on every non-coupled patch
+ * (OpenFOAM's default for nut: the stored boundary_nut is kept, zero unless set) */
 int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* patch_type);
 /* a patch parameter of a mixed condition: (field "p", name "gamma") of waveTransmissive */
 int dfmi_set_patch_param(dfmi_ctx* ctx, const char* field, int patch, const char* name, double value);
@@ -144,7 +146,8 @@ int dfmi_thermo_load(dfmi_ctx* ctx, const char* thermo_coeff_file);
  *        faces  phi phi_old phiUc rhorAUf phiHbyA
  *        boundary_<name> for the boundary counterparts; boundary-only: boundary_heGradient,
  *        boundary_{U,p,Y,K}_ref (inletOutlet inletValue), boundary_p_vf (waveTransmissive valueFraction),
- *        boundary_p_gamma, chem_stats [3][C]. count = values per component. */
+ *        boundary_p_gamma, chem_stats [3][C]. count = values per component.
+ *        LES: delta (cells; positive), nut (cells; get only), boundary_nut (set: the fixedValue / calculated slots). */
 int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long count, int layout);
 int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, int layout);
 
@@ -154,6 +157,26 @@ int dfmi_rho_process(dfmi_ctx* ctx);            /* dfRhoEqn::process (dfRhoEqn.c
 int dfmi_U_process(dfmi_ctx* ctx);              /* dfUEqn::process (dfUEqn.cu:487-689) */
 int dfmi_Y_process(dfmi_ctx* ctx);              /* dfYEqn::process (dfYEqn.cu:443-695); RR from dfmi_set_field("RR") or the chemistry */
 int dfmi_E_process(dfmi_ctx* ctx);              /* dfEEqn::process (dfEEqn.cu:108-264) */
+/* ---- LES eddy viscosity: turbulence->correct() (dfLowMachFoam.C:508). Every equation of the reference goes through
+ * turbulence-> (UEqn.H:6 divDevRhoReff(U); YEqn.H:96 DEff = rhoD(i) + mut/Sct; EEqn.H:20-37 laplacian(alphaEff, he));
+ * its GPU path carries a Smagorinsky kernel it never calls (src_gpu/dfUEqn.cu:305-353). Options (dfmi_set_option):
+ *   les.model  0 laminar (default) | 1 Smagorinsky | 2 WALE (OpenFOAM-7 LESeddyViscosity; anything else is refused)
+ *   les.Ck 0.094, les.Ce 1.048 (Smagorinsky), les.Cw 0.325 (WALE), les.Prt 1, les.Sct 1 (createFields.H:133)
+ * With g = grad(U) (the UEqn's Gauss linear gradient), D = symm(g) and the field "delta":
+ *   Smagorinsky  a = Ce/delta, b = (2/3) tr D, c = 2 Ck delta (dev(D) && D), k = ((-b + sqrt(b^2 + 4ac)) / (2a))^2
+ *   WALE         Sd = dev(symm(g.g)), m = Sd && Sd, s = D && D, k = (Cw^2 delta/Ck)^2 m^3 / ((s^(5/2) + m^(5/4))^2 + 1e-15)
+ *   nut = Ck delta sqrt(k); boundary_nut = nut.correctBoundaryConditions() by the patch types of "nut".
+ * This call forms nut and boundary_nut from U / boundary_U as they stand (several ranks: a collective, the processor
+ * slots' neighbour half is exchanged). dfmi_time_step runs it after the last pressure corrector, and first thing when
+ * nut is not valid (turbulence->validate(), dfLowMachFoam.C:207): after les.model or a coefficient changed, "delta"
+ * was set, or "U" / "boundary_U" were written through dfmi_set_field. With les.model != 0 the three assemblies read
+ *   mut = rho nut, muEff = mut + mu, alphaEff = alpha + mut/Prt, DEff_i = rhoD_i + mut/Sct
+ * (rho after the rhoEqn; on boundary slots from the slot's own values) and drop what the reference drops for
+ * simulationType != laminar: fvmDiv(phiUc, Yi) (YEqn.H:101-106), diffAlphaD and div(hDiffCorrFlux) (EEqn.H:30-36) --
+ * the YEqn preparation kernel is not launched and sumYDiffError, hDiffCorrFlux, diffAlphaD, phiUc read back as zeros.
+ * dfmi_U_process / dfmi_Y_process / dfmi_E_process / dfmi_assemble use the nut in the context and fail when it is not
+ * valid. les.model = 0: a successful no-op. */
+int dfmi_turbulence_correct(dfmi_ctx* ctx);
 int dfmi_thermo_correct(dfmi_ctx* ctx);         /* dfThermo::correctThermo (dfThermo.cu:572-671) */
 int dfmi_thermo_update_energy(dfmi_ctx* ctx);   /* he, psi, rho, transport from T (dfThermo::updateEnergy) */
 int dfmi_thermo_update_rho(dfmi_ctx* ctx);      /* dfThermo::updateRho (:673-679) */
@@ -203,7 +226,7 @@ int dfmi_step_times(dfmi_ctx* ctx, double* ms, int n, int* got);
  * times by a 16-B-vector streaming kernel -- the measured peak beside the datasheet's 8 TB/s */
 int dfmi_hbm_copy_peak(dfmi_ctx* ctx, double gib, int reps, double* gbs);
 /* correct_boundary_conditions_{scalar,vector} (dfMatrixOpBase.cu:2402-2491) for field in
- * {"U","p","he","T","rho","K","Y"} using that field's patch types */
+ * {"U","p","he","T","rho","K","Y","nut"} using that field's patch types */
 int dfmi_correct_boundary(dfmi_ctx* ctx, const char* field);
 
 /* ---- matrix inspection (the reference DEBUG_CHECK_LDU / compareResult path, dfYEqn.cu:566-572) */
@@ -230,6 +253,7 @@ int dfmi_set_preconditioner(dfmi_ctx* ctx, const char* eqn, const char* name);
  * refused, and so is 1 together with global_coarse),
  * "solver.*" (even_odd, small, row_classes), "pcg.*" (face_form, fuse_l0), "fv.*" (hex_walk, csr_walk,
  * species_generic, yprep_brick), "chem.*" (method 0 ROS3 | 1 extrapolation, generated, binning),
+ * "les.*" (model, Ck, Ce, Cw, Prt, Sct: dfmi_turbulence_correct above),
  * "dnn.tuned_gemm", "step.courant" (1: dfmi_time_step queues the Courant-number kernel behind its last
  * kernel and posts the result to pinned memory for dfmi_courant_no; 0, the default: nothing added); keys and
  * defaults in INTEGRATION.md. Solver-structure keys must be set before the first solve; unknown keys fail. */
