@@ -32,7 +32,7 @@ struct MeshView {
   int C, F, B, S;
   const int *own, *nei, *ownStart, *nbrStart, *nbrFace, *cbStart, *cbSlot, *bfc, *partner;
   int fslot;                // face storage in owner-slot order (k*C + c) rather than OpenFOAM order
-  const int8_t* sprim;   // 1 = primary slot (owner side), 0 = processor [internal n] slot
+  const int8_t* sprim;   // != 0: primary slot (2: of a processor patch towards a lower rank), 0 = processor [internal n] slot
   const double *Sf, *magSf, *w, *dc, *V, *bSf, *bmagSf, *bw, *bdc;
   // solver gather rows [W][C] (linsolve.hip build_ell): the face loops read them. Entry k of cell c's row is
   // column ecol[k C + c] and coefficient source esrc[k C + c] (2 f + own for the face at storage f, -(b + 1)

@@ -85,6 +85,18 @@ __device__ __forceinline__ double bface(const MeshView& m, int t, const double* 
   return bc_coupled(t) ? interp_b(m.bw[b], vf[c], nbrv(m, vf, bvf, b)) : bvf[b];
 }
 
+// upwind weight of a slot's own cell from the flux out of it. A flux of exactly zero gives the weight 1 to the
+// cell, as an internal face gives it to its owner -- except on the higher rank's side of a processor face
+// (MeshView::sprim == 2, halo_setup), so that one rank only calls itself upwind there: what rides on that weight
+// without being phi (the YEqn's phiUc) would otherwise be convected out of both cells. Cyclic and processorCyclic
+// faces keep the weight 1 on both halves, which is what a single domain computes for a cyclic pair.
+__device__ __forceinline__ double upwind_b(const MeshView& m, const double* __restrict__ bphi, int b) {
+  const double ph = bphi[b];
+  if (ph > 0) return 1.0;
+  if (ph < 0) return 0.0;
+  return m.sprim[b] == 2 ? 0.0 : 1.0;
+}
+
 // visit faces of cell c in sequential order: fn(face, other_cell, is_owner).
 // WT > 0 (meshes whose busiest cell has WT couplings, hex meshes: 6): read the cell's row of the solver
 // gather (ELL [W][C], built once: neighbour faces ascending, owned faces ascending, then coupled slots)
@@ -347,7 +359,7 @@ __global__ void k_conv_w_slot(MeshView m, int S, const int8_t* __restrict__ tyY,
       }
     }
   }
-  bwout[b] = lim * m.bw[b] + (1 - lim) * pos0(ph);
+  bwout[b] = lim * m.bw[b] + (1 - lim) * upwind_b(m, bphi, b);
 }
 
 // gradients of every field of the table at the cells of the processor slots -> g [3(S+1)][C] (only those
@@ -470,7 +482,7 @@ __global__ void k_lim_w_slot(MeshView m, const int8_t* __restrict__ ty, int b01,
       lim = ll_limiter(twoByk, ph, v[c], vn, gu, dv);
     }
   }
-  bwout[b] = lim * m.bw[b] + (1 - lim) * pos0(ph);
+  bwout[b] = lim * m.bw[b] + (1 - lim) * upwind_b(m, bphi, b);
 }
 
 __global__ void k_upwind_w_face(MeshView m, const double* __restrict__ phi, double* __restrict__ wout) {
@@ -481,7 +493,7 @@ __global__ void k_upwind_w_face(MeshView m, const double* __restrict__ phi, doub
 __global__ void k_upwind_w_slot(MeshView m, const double* __restrict__ bphi, double* __restrict__ bwout) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= m.B) return;
-  bwout[b] = pos0(bphi[b]);
+  bwout[b] = upwind_b(m, bphi, b);
 }
 
 // limitedLinearV weights of div(phi,U) (limitedLinearLimiter<NVDVTVDV>) from grad(U) g [9][C]
@@ -534,7 +546,7 @@ __global__ void k_llv_w_slot(MeshView m, const int8_t* __restrict__ ty, double t
     for (int q = 0; q < 9; ++q) gu[q] = g[q * C + cu];
     lim = llv_limiter(twoByk, vP, vN, gu, dv);
   }
-  bwout[b] = lim * m.bw[b] + (1 - lim) * pos0(ph);
+  bwout[b] = lim * m.bw[b] + (1 - lim) * upwind_b(m, bphi, b);
 }
 
 // cubic::correction of a vector field (3 components), dotted with Sf: the flux cubic adds to the linear
@@ -1565,7 +1577,7 @@ __global__ void __launch_bounds__(TPB) k_y_assemble(MeshView m, const int8_t* __
     src[s * C + c] = ro * Y[s * C + c] * vol + vol * RR[s * C + c];
   }
   each_slot(m, tyY, c, [&](int b, int t) {
-    const double wu = bwY ? bwY[b] : (bphi[b] >= 0 ? 1.0 : 0.0);
+    const double wu = bwY ? bwY[b] : upwind_b(m, bphi, b);
 #pragma unroll
     for (int s = 0; s < S; ++s) {
       if (s == inert) continue;
@@ -1642,7 +1654,7 @@ __global__ void __launch_bounds__(TPB) DFMI_WAVES(5) k_y_assemble_ell(MeshView m
     sr[s] = ro * Y[s * C + c] * vol + vol * RR[s * C + c];
   }
   each_slot(m, tyY, c, [&](int b, int t) {
-    const double wu = bwY ? bwY[b] : (bphi[b] >= 0 ? 1.0 : 0.0);
+    const double wu = bwY ? bwY[b] : upwind_b(m, bphi, b);
     const bool cp = bc_coupled(t);
 #pragma unroll
     for (int s = 0; s < S; ++s) {
@@ -1949,7 +1961,7 @@ __global__ void __launch_bounds__(TPB) k_y_assemble_gen(MeshView m, int S, const
       src[s * C + c] = ro * Y[s * C + c] * vol + vol * RR[s * C + c];
     }
     each_slot(m, tyY, c, [&](int b, int t) {
-      const double wu = bwY ? bwY[b] : (bphi[b] >= 0 ? 1.0 : 0.0);
+      const double wu = bwY ? bwY[b] : upwind_b(m, bphi, b);
 #pragma unroll
       for (int j = 0; j < CH; ++j) {
         const int s = s0 + j;
@@ -2031,7 +2043,7 @@ __global__ void __launch_bounds__(TPB) k_y_assemble_ell_gen(MeshView m, int s_lo
       sr[j] = s < S ? ro * Y[s * C + c] * vol + vol * RR[s * C + c] : 0.0;
     }
     each_slot(m, tyY, c, [&](int b, int t) {
-      const double wu = bwY ? bwY[b] : (bphi[b] >= 0 ? 1.0 : 0.0);
+      const double wu = bwY ? bwY[b] : upwind_b(m, bphi, b);
       const bool cp = bc_coupled(t);
 #pragma unroll
       for (int j = 0; j < CH; ++j) {

@@ -419,6 +419,17 @@ void halo_setup(Ctx& x) {
   }
   x.H = (int)cells.size();
   h.h_cells = cells;
+  {   // primary slots of processor patches towards a lower rank: 2 (upwind_b: a zero flux is the lower rank's).
+      // processorCyclic patches keep 1 on both sides, as the two halves of a cyclic pair do on one rank
+    std::vector<int8_t> prim(std::max(x.B, 1), 0);
+    auto pc = x.ptype.find("calculated");
+    for (int p = 0; p < x.P; ++p) {
+      const bool plain = pc != x.ptype.end() && pc->second[p] == PROCESSOR;
+      const int8_t v = (x.pkind[p] == 2 && plain && x.peer[p] < x.rank) ? 2 : 1;
+      for (int i = 0; i < x.psize[p]; ++i) prim[x.poff[p] + i] = v;
+    }
+    x.sprim.upload(prim.data(), (size_t)x.B, x.stream);
+  }
   h.slots.build(s_cells, r_slots, x.stream);
   h.vec.build(s_cells, r_halo, x.stream);
   h.have_split = false;

@@ -10,7 +10,9 @@ it was built from) and two ranks.
 
 Meshes: (a) hex_box(20, 20, 14) periodic, y-grading 1.3 (test_gpu_amg_tail's, 5600 cells: three levels);
 (b) hex_box(21, 20, 14) periodic (the odd periodic direction forces a third colour); (c) hex_box(11, 9, 7) with
-the audit test's mixed walls (693 cells: the one-workgroup small solve has to be bypassed).
+the audit test's mixed walls (693 cells: the one-workgroup small solve has to be bypassed); (d) the 2:1 refined box
+of tests/unstructured_meshes.py with the same walls (243 cells, W = 9, a graph with triangles; coarsened to 64 cells
+so that it has levels).
 """
 import os
 import threading
@@ -52,7 +54,12 @@ def _audit_case(mesh, opts):
     from test_gpu_solver_audit import _audit_state, _mixed_walls
     kw = {"a": dict(nx=20, ny=20, nz=14, gradings=(1.0, 1.3, 1.0), mech="burke9"),
           "b": dict(nx=21, ny=20, nz=14, gradings=(1.0, 1.0, 1.0), mech="burke9"),
-          "c": dict(nx=11, ny=9, nz=7, periodic=False, walls=_mixed_walls, mixed=True, mech="burke9")}[mesh]
+          "c": dict(nx=11, ny=9, nz=7, periodic=False, walls=_mixed_walls, mixed=True, mech="burke9"),
+          "d": dict(periodic=False, walls=_mixed_walls, mixed=True, mech="burke9")}[mesh]
+    if mesh == "d":
+        import unstructured_meshes as um
+        kw["mesh"] = um.get("refined")
+        opts = dict(opts, **{"amg.coarsest_size": 64})
     with _options(opts):
         ctx, m, t, st, pt, inert, dt = _case(**kw)
     st = _audit_state(ctx, m, t, st, inert)
@@ -185,10 +192,10 @@ def test_default_path_is_bitwise_untouched():
         assert np.array_equal(a[k], b[k]), k
 
 
-@pytest.mark.parametrize("mesh", ["a", "b", "c"])
+@pytest.mark.parametrize("mesh", ["a", "b", "c", "d"])
 def test_colouring_and_factor(mesh):
     """level 0 in fp64 against the recurrence (bound: _check_factor); every coarser level has E > 0 and a
-    non-empty colour 0"""
+    non-empty colour 0. (d): an irregular graph -- the colour count is printed and held to W + 1 only"""
     ctx, m, t, st, pt, inert, W = _audit_case(mesh, {"amg.smoother": 1, "amg.precision": 64})
     _up_to_p(ctx)
     ctx.call("p_process")
@@ -201,6 +208,8 @@ def test_colouring_and_factor(mesh):
     if mesh == "b":
         assert ncol == 3
     levels = ctx.amg_info()
+    if mesh == "d":
+        assert len(levels) >= 2 and levels[0] == (m.n_cells, 9), levels
     for l in range(1, len(levels)):
         cl, El = ctx.amg_smoother_info(l)
         print(f"mesh ({mesh}) level {l}: {levels[l]} colours {np.bincount(cl).tolist()} E min {El.min():.3e}")

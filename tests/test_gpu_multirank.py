@@ -236,12 +236,17 @@ def _distorted_polymesh(nx, ny, nz, periodic, distort=0.15, seed=5):
     return d, (P, faces, own, nei, bnd), read_polymesh(os.path.join(d, "constant", "polyMesh"))
 
 
-@pytest.mark.parametrize("method,nparts,from_dirs", [("rcb", 3, False), ("graph", 4, True)])
-def test_partitioned_polymesh_matches_oracle(method, nparts, from_dirs):
+@pytest.mark.parametrize("method,nparts,from_dirs,mesh", [("rcb", 3, False, "distorted"), ("graph", 4, True, "distorted"),
+                                                          ("graph", 2, False, "refined")],
+                         ids=["rcb-3-False", "graph-4-True", "refined-graph-2"])
+def test_partitioned_polymesh_matches_oracle(method, nparts, from_dirs, mesh):
     """An arbitrary (non-orthogonal, read from constant/polyMesh) mesh cut by the partitioners
     (dfmi/partition.py: RCB / recursive graph bisection; processor + processorCyclic patches), optionally
     through processor* directories written and read back; the decomposed run equals the oracle's
-    single-domain step."""
+    single-domain step. "refined": the 2:1 refined box of tests/unstructured_meshes.py (W = 9, hanging nodes) --
+    processor patches with faces of unequal size and halo columns in rows of unequal length; its cut crosses
+    z-normal faces off the Taylor-Green symmetry plane, whose flux is exactly zero while phiUc is not (both ranks
+    once took the upwind weight there: T off by 6.5e-7, U by 3.7e-4)."""
     import oracle as O
     from dfmi import case
     from dfmi.mech import read_thermo_table, read_yaml_mechanism
@@ -249,7 +254,11 @@ def test_partitioned_polymesh_matches_oracle(method, nparts, from_dirs):
     ym = read_yaml_mechanism(os.path.join(GOLDEN, "ES80_H2-7-16.yaml"))
     t = read_thermo_table(os.path.join(GOLDEN, "thermo_ES80_H2-7-16.txt"), ym["species"])
     dt = 1e-6
-    d, raw, mg = _distorted_polymesh(8, 6, 5, (True, False, True))
+    if mesh == "refined":
+        import unstructured_meshes as um
+        d, raw, mg = None, None, um.get("refined")
+    else:
+        d, raw, mg = _distorted_polymesh(8, 6, 5, (True, False, True))
     f = case.tgv_fields(mg, ym["species"], kernel_radius=1.2e-3)
     ctx = _setup(mg, t, ym, dt)
     case.init_state(ctx, mg, t.S, f["T"], f["p"], f["U"], f["Y"])
@@ -265,7 +274,11 @@ def test_partitioned_polymesh_matches_oracle(method, nparts, from_dirs):
         meshes = read_decomposed(d)
     else:
         meshes = decompose(mg, part)
-    assert any(p.kind == "processorCyclic" for mm in meshes for p in mm.patches)
+    if mesh == "refined":
+        assert all(np.unique(np.round(p.mag_sf / p.mag_sf.max(), 6)).size > 1
+                   for mm in meshes for p in mm.patches if p.kind == "processor")
+    else:
+        assert any(p.kind == "processorCyclic" for mm in meshes for p in mm.patches)
     nr = len(meshes)
     out, err = [None] * nr, [None] * nr
     hub = _HUB[0]; _HUB[0] += 1

@@ -47,13 +47,15 @@ def _distorted_mesh(nx, ny, nz, lengths, seed=5, amp=0.15):
 
 
 def _case(nx=6, ny=5, nz=4, periodic=True, walls=None, gradings=(1.0, 1.4, 1.0), mech="es80", distorted=False,
-          renumber=None, mixed=False, traversal=False, schemes=None):
+          renumber=None, mixed=False, traversal=False, schemes=None, mesh=None):
     from dfmi.mesh import hex_box, FIXED_VALUE, ZERO_GRADIENT
     from dfmi.lib import Context
     from dfmi import case
     ym, t = _mech(mech)
     L = 1e-3
-    if distorted:
+    if mesh is not None:   # a prebuilt Mesh (tests/unstructured_meshes.py)
+        m = mesh
+    elif distorted:
         m = _distorted_mesh(nx, ny, nz, (2 * np.pi * L,) * 3)
     else:
         m = hex_box(nx, ny, nz, lengths=(2 * np.pi * L,) * 3, periodic=(periodic,) * 3, gradings=gradings)

@@ -42,7 +42,7 @@ pytestmark = pytest.mark.gpu
 L = 2 * np.pi * 1e-3
 PT_KEY = {"U": "U", "Y": "Y", "E": "he", "p": "p"}
 FIELD = {"U": "U", "Y": "Y", "E": "he", "p": "p"}
-TIMED = "k_bcg_eo,k_bcg_spmv,k_bcg_small,k_pcg_small,k_cg_spmv,k_cg_x,k_cg_x_smooth,k_vtail"
+TIMED = "k_bcg_eo,k_bcg_spmv,k_bcg_small,k_pcg_small,k_cg_spmv,k_cg_x,k_cg_x_smooth,k_vtail,k_dilu_fwd"
 PRODUCTION = (1e-5, 20, 1000)
 TIGHT = (1e-9, 300, 3000)
 
@@ -203,18 +203,45 @@ CASES = {
 }
 
 
+def _unstructured(name):
+    """kwargs of _case for a mesh of tests/unstructured_meshes.py (built when the case runs)"""
+    def mesh():
+        import unstructured_meshes as um
+        return um.get(name)
+    return dict(periodic=False, walls=_walls, mech="burke9", mesh=mesh)
+
+
+# prisms (W = 5), prisms and hexahedra (W = 6, not a hex box), a 2:1 refined box (W = 9): none of them 2-colours, so
+# the batched BiCGStab keeps the Jacobi path; the AMG is coarsened to 64 cells so that these sizes have levels
+UNSTRUCTURED = {"solver.small": 0, "amg.coarsest_size": 64}
+CASES.update({
+    "prisms": (_unstructured("prisms"), UNSTRUCTURED, ("k_bcg_spmv", "k_cg_spmv"), ("k_bcg_eo", "k_bcg_small", "k_pcg_small")),
+    "hexprism": (_unstructured("hexprism"), UNSTRUCTURED, ("k_bcg_spmv", "k_cg_spmv"), ("k_bcg_eo", "k_bcg_small", "k_pcg_small")),
+    "refined": (_unstructured("refined"), UNSTRUCTURED, ("k_bcg_spmv", "k_cg_spmv"), ("k_bcg_eo", "k_bcg_small", "k_pcg_small")),
+    "refined-one-workgroup": (_unstructured("refined"), {"amg.coarsest_size": 64}, ("k_bcg_small", "k_pcg_small"),
+                              ("k_bcg_eo", "k_bcg_spmv", "k_cg_spmv")),
+    "refined-dilu": (_unstructured("refined"), dict(UNSTRUCTURED, **{"amg.smoother": 1}), ("k_bcg_spmv", "k_cg_spmv", "k_dilu_fwd"),
+                     ("k_bcg_eo", "k_cg_x_smooth", "k_vtail", "k_pcg_small")),
+})
+UNSTRUCTURED_W = {"prisms": 5, "hexprism": 6, "refined": 9}
+
+
 @pytest.mark.parametrize("name", list(CASES))
 def test_solver_paths_report_the_true_residual(name, monkeypatch):
     from dfmi import case, lib
     kw, opts, ran, not_ran = CASES[name]
     for k, v in opts.items():
         monkeypatch.setitem(lib.DEFAULT_OPTIONS, k, v)
+    if callable(kw.get("mesh")):
+        kw = dict(kw, mesh=kw["mesh"]())
     ctx, m, t, st, pt, inert, dt = _case(**kw)
     if name == "pcg-jacobi":
         ctx.set_preconditioner("p", "jacobi")
     if name == "non-hex":
         assert ctx.hex_dims() == (0, 0, 0)
     W = _ell_width(m)
+    if name.split("-")[0] in UNSTRUCTURED_W:
+        assert ctx.hex_dims() == (0, 0, 0) and W == UNSTRUCTURED_W[name.split("-")[0]]
     st = _audit_state(ctx, m, t, st, inert, own_species=name == "gri53")
     # 1-3 at the production tolerance, with the path's kernels counted
     ctx.kernel_timer(TIMED)

@@ -69,7 +69,7 @@ def _nut_patches(m):
 
 
 class Case:
-    def __init__(self, param):
+    def __init__(self, param, mesh=None):
         from dfmi import case, lib, turbulence as T
         self.param = param
         generic = param.endswith("-generic")
@@ -85,7 +85,7 @@ class Case:
                 r = _case(mech=mech, schemes=self.schemes)
             else:
                 r = _case(periodic=False, walls=_walls(mixed=kind == "mixed"), mech=mech, distorted=kind == "distorted",
-                          mixed=kind == "mixed", schemes=self.schemes)
+                          mixed=kind == "mixed", schemes=self.schemes, mesh=mesh)
         finally:
             lib.DEFAULT_OPTIONS.pop("fv.species_generic", None)
         self.ctx, self.m, self.t, st, self.pt, self.inert, self.dt = r
