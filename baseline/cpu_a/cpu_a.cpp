@@ -1124,6 +1124,12 @@ int dfmi_set_scheme(dfmi_ctx* ctx, const char* term, const char* scheme) {
     }
     if (!tok.empty() && tok[0] == "Gauss") tok.erase(tok.begin());
     CHECK(!tok.empty(), t + ": empty scheme");
+    if (t == "laplacian") {   // CPU-A assembles Gauss linear orthogonal only: any other laplacian scheme is refused
+      if (tok[0] == "linear") tok.erase(tok.begin());
+      CHECK(tok.size() == 1 && tok[0] == "orthogonal",
+            "laplacian: CPU-A implements 'orthogonal' only (uncorrected / corrected: the HIP library)");
+      return;
+    }
     int kind = -1;
     double k = 1.0;
     if (tok[0] == "upwind") kind = 0;

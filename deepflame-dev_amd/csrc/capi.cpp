@@ -151,16 +151,21 @@ void copy_field(Ctx& x, const std::string& name, const double* host, long count,
   Field& f = it->second;
   if (f.face) {   // OpenFOAM face order on the host, owner-slot storage on the device
     DFMI_CHECK(count == x.F, "field '" + name + "': expected " + std::to_string(x.F) + " values, got " + std::to_string(count));
-    std::vector<double> st(f.n, 0.0);
+    // component k of face i: host[k F + i], or host[i ncomp + k] (DFMI_AOS vectors); device [ncomp][Fs]
+    const int nc = f.ncomp;
+    const bool aos = layout == DFMI_AOS && nc == 3;
+    std::vector<double> st((size_t)f.n * nc, 0.0);
     if (to_dev) {
-      for (long i = 0; i < x.F; ++i) st[x.h_fst[i]] = host[i];
-      DFMI_HIP(hipMemcpyAsync(f.buf.p, st.data(), f.n * sizeof(double), hipMemcpyHostToDevice, x.stream));
+      for (int k = 0; k < nc; ++k)
+        for (long i = 0; i < x.F; ++i) st[k * f.n + x.h_fst[i]] = aos ? host[i * nc + k] : host[k * x.F + i];
+      DFMI_HIP(hipMemcpyAsync(f.buf.p, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice, x.stream));
       DFMI_HIP(hipStreamSynchronize(x.stream));
     } else {
-      DFMI_HIP(hipMemcpyAsync(st.data(), f.buf.p, f.n * sizeof(double), hipMemcpyDeviceToHost, x.stream));
+      DFMI_HIP(hipMemcpyAsync(st.data(), f.buf.p, st.size() * sizeof(double), hipMemcpyDeviceToHost, x.stream));
       DFMI_HIP(hipStreamSynchronize(x.stream));
       double* out = const_cast<double*>(host);
-      for (long i = 0; i < x.F; ++i) out[i] = st[x.h_fst[i]];
+      for (int k = 0; k < nc; ++k)
+        for (long i = 0; i < x.F; ++i) (aos ? out[i * nc + k] : out[k * x.F + i]) = st[k * f.n + x.h_fst[i]];
     }
     return;
   }
@@ -197,6 +202,22 @@ void require_ready(Ctx& x) {
 }
 
 void maybe_setup_halo(Ctx& x);
+
+// The non-orthogonal geometry belongs to Sf, mesh_distance and the patch deltas as they stood when it was formed: an
+// initialiser that is called again re-forms it, or, where what it needs is gone (no mesh_distance any more), puts the
+// laplacian scheme back to orthogonal
+void nonorth_refresh(Ctx& x) {
+  if (!x.no_dc) return;
+  bool coupled = false;
+  for (int p = 0; p < x.P; ++p) coupled |= x.pkind[p] != 0;
+  if (x.have_geom && x.have_bgeom && x.have_md && (!coupled || x.have_bdelta)) {
+    nonorth_setup(x);
+    DFMI_HIP(hipStreamSynchronize(x.stream));
+  } else {
+    x.lap = LAP_ORTHOGONAL;
+    x.no_dc = x.no_bdc = x.no_k = x.no_bk = nullptr;
+  }
+}
 
 // ---- equation drivers
 void do_U(Ctx& x) {
@@ -310,7 +331,30 @@ void do_U_Y_E(Ctx& x, bool hbya = false) {
   e_assemble_back(x);
   do_E_back(x);
 }
+// pEqn.H:51-62, while (pimple.correctNonOrthogonal()): the matrix is assembled once; each of the 1 + p.n_nonorth passes
+// forms the explicit non-orthogonal term from p as it stands (corrected only) and solves. The last pass's face flux
+// correction enters phi = phiHbyA + pEqn.flux(). The solver's fused setup (pcg.fuse_setup) is bypassed here: the
+// source is re-formed between the cell pass and every solve.
+void do_p_nonorth(Ctx& x, int n_nonorth) {
+  const bool corr = x.lap == LAP_CORRECTED;
+  p_assemble(x, true);
+  Matrix& A = x.mP;
+  if (corr) nonorth_p_base(x);
+  for (int i = 0; i <= n_nonorth; ++i) {
+    if (corr) nonorth_p_correct(x);
+    solve_pcg(x, "p", A.lower, A.upper, A.diag, A.source, A.ic, A.bc, "p", x.f("p"), x.f("boundary_p"), x.solver["p"],
+              false);
+    if (i < n_nonorth) {   // the next pass's gradient reads p's boundary values
+      k_bc_correct(x, "p", x.f("p"), x.f("boundary_p"), 1);
+      halo_fields(x, {"p"});
+    }
+  }
+  p_post_solve(x);
+  if (corr) nonorth_p_flux(x);
+}
 void do_p(Ctx& x) {
+  const int n_nonorth = (int)x.opt("p.n_nonorth");
+  if (x.lap == LAP_CORRECTED || n_nonorth > 0) { do_p_nonorth(x, n_nonorth); return; }
   // face-form PCG with the reused V-cycle: the solver's setup kernel does the cell pass too (pcg.fuse_setup)
   const bool fuse = pcg_setup_fusable(x, x.solver["p"]);
   p_assemble(x, !fuse);
@@ -460,6 +504,7 @@ int dfmi_init_constant_fields_internal(dfmi_ctx* ctx, const double* sf, const do
     DFMI_HIP(hipStreamSynchronize(x.stream));
     x.have_md = mesh_distance != nullptr;
     x.have_geom = true;
+    nonorth_refresh(x);
   });
 }
 
@@ -488,6 +533,7 @@ int dfmi_init_constant_fields_boundary(dfmi_ctx* ctx, const double* bsf, const d
     DFMI_HIP(hipStreamSynchronize(x.stream));
     x.have_bgeom = true;
     maybe_setup_halo(x);
+    nonorth_refresh(x);
   });
 }
 
@@ -527,6 +573,7 @@ int dfmi_init_boundary_delta(dfmi_ctx* ctx, const double* boundary_delta) {
     x.bdv.upload(soa, x.stream);
     DFMI_HIP(hipStreamSynchronize(x.stream));
     x.have_bdelta = true;
+    nonorth_refresh(x);
   });
 }
 
@@ -556,12 +603,40 @@ static void parse_scheme(const std::string& term, const std::string& text, int& 
   DFMI_CHECK(tok.size() == 1, term + ": unexpected arguments in '" + text + "'");
 }
 
+// laplacianSchemes default: "[Gauss] [linear] orthogonal | uncorrected | corrected" (one scheme for the U, Yi, he and p
+// laplacians). Everything is checked before the context changes, so a refused scheme leaves the one in force.
+static void set_laplacian(Ctx& x, const std::string& text) {
+  std::vector<std::string> tok;
+  std::string cur;
+  for (char ch : text + " ") {
+    if (ch == ' ' || ch == '\t') { if (!cur.empty()) tok.push_back(cur); cur.clear(); }
+    else cur += ch;
+  }
+  if (!tok.empty() && tok[0] == "Gauss") tok.erase(tok.begin());
+  if (!tok.empty() && tok[0] == "linear") tok.erase(tok.begin());
+  DFMI_CHECK(!tok.empty(), "laplacian: empty scheme");
+  DFMI_CHECK(tok[0] != "limited", "laplacian: the snGrad scheme 'limited' is not supported (orthogonal, uncorrected or corrected)");
+  const int lap = tok[0] == "orthogonal" ? LAP_ORTHOGONAL : tok[0] == "uncorrected" ? LAP_UNCORRECTED
+                  : tok[0] == "corrected" ? LAP_CORRECTED : -1;
+  DFMI_CHECK(lap >= 0, "laplacian: unsupported scheme '" + text + "' (orthogonal, uncorrected or corrected)");
+  DFMI_CHECK(tok.size() == 1, "laplacian: unexpected arguments in '" + text + "'");
+  if (lap != LAP_ORTHOGONAL) {
+    bool coupled = false;
+    for (int p = 0; p < x.P; ++p) coupled |= x.pkind[p] != 0;
+    DFMI_CHECK(x.have_md, "laplacian " + tok[0] + " needs mesh_distance (dfmi_init_constant_fields_internal)");
+    DFMI_CHECK(!coupled || x.have_bdelta, "laplacian " + tok[0] + " on a mesh with coupled patches needs dfmi_init_boundary_delta");
+    if (!x.no_dc) { nonorth_setup(x); DFMI_HIP(hipStreamSynchronize(x.stream)); }   // the geometry is formed once
+  }
+  x.lap = lap;
+}
+
 int dfmi_set_scheme(dfmi_ctx* ctx, const char* term, const char* scheme) {
   return guard([&] {
     Ctx& x = ctx->x;
     // the patch kinds (processor patches) are known only after the boundary initialisation
     DFMI_CHECK(x.have_bgeom, "call dfmi_init_constant_fields_boundary before dfmi_set_scheme");
     const std::string t(term ? term : ""), s(scheme ? scheme : "");
+    if (t == "laplacian") { set_laplacian(x, s); return; }
     int kind;
     double k;
     parse_scheme(t, s, kind, k);
@@ -580,7 +655,7 @@ int dfmi_set_scheme(dfmi_ctx* ctx, const char* term, const char* scheme) {
       for (int p : x.pkind) proc |= p == 2;
       DFMI_CHECK(kind == SCH_LINEAR || !proc, t + ": limited schemes on decomposed meshes (processor patches) are not supported");
       x.sch.U = kind; x.sch.k_U = k;
-    } else throw Error("dfmi: unknown scheme term '" + t + "' (div(phi,Yi_h), div(phi,K), div(hDiffCorrFlux), div(phi,U))");
+    } else throw Error("dfmi: unknown scheme term '" + t + "' (div(phi,Yi_h), div(phi,K), div(hDiffCorrFlux), div(phi,U), laplacian)");
   });
 }
 
@@ -664,6 +739,8 @@ int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long cou
     const std::string n(name ? name : "");
     if (n == "delta" || n == "nut" || n == "boundary_nut") ensure_les_fields(x);
     DFMI_CHECK(n != "nut", "field 'nut' is formed by dfmi_turbulence_correct and cannot be set (boundary_nut holds the fixed-value slots)");
+    DFMI_CHECK(n.rfind("nonorth_", 0) != 0 && n.rfind("boundary_nonorth_", 0) != 0,
+               "field '" + n + "' is formed by the library (dfmi_set_scheme \"laplacian\") and cannot be set");
     if (n == "delta") {
       DFMI_CHECK(count == x.C, "field 'delta': expected " + std::to_string(x.C) + " values, got " + std::to_string(count));
       for (long i = 0; i < count; ++i)
@@ -967,7 +1044,11 @@ int dfmi_assemble(dfmi_ctx* ctx, const char* eqn) {
       y_prep(x); y_assemble(x);
       bicg_rows_from_ldu_Y(x);
     } else if (e == "E") { conv_weights(x); e_assemble(x); }   // EEqn inspected on its own: fresh div(phi,Yi_h) weights
-    else if (e == "p") p_assemble(x);
+    else if (e == "p") {
+      p_assemble(x);
+      // corrected laplacian: the source of the corrector loop's first pass (do_p_nonorth)
+      if (x.lap == LAP_CORRECTED) { nonorth_p_base(x); nonorth_p_correct(x); }
+    }
     else if (e == "HbyA") u_hbya(x);
     else if (e == "p_post") p_post_solve(x);
     else if (e == "Y_post") y_post_solve(x);
@@ -1228,6 +1309,9 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
     const bool global = k == "amg.global_coarse" ? value != 0.0 : x.on("amg.global_coarse");
     DFMI_CHECK(!((k == "amg.smoother" || k == "amg.global_coarse") && dilu && global),
                "dfmi_set_option: amg.smoother = 1 (multicolour DILU) and amg.global_coarse = 1 exclude each other");
+    if (k == "p.n_nonorth")
+      DFMI_CHECK(value >= 0 && value <= 1000 && value == (double)(int)value,
+                 "dfmi_set_option: p.n_nonorth (nNonOrthogonalCorrectors) must be an integer >= 0");
     if (k.rfind("les.", 0) == 0) {
       if (k == "les.model")
         DFMI_CHECK(value == 0.0 || value == 1.0 || value == 2.0,

@@ -277,6 +277,8 @@ inline const OptDef* option_defs(int& n) {
     {"les.Cw", 0.325},                // WALE
     {"les.Prt", 1.0},                 // alphaEff = alpha + mut / Prt (createFields.H:133)
     {"les.Sct", 1.0},                 // DEff_i = rhoD_i + mut / Sct
+    {"p.n_nonorth", 0},               // nNonOrthogonalCorrectors (system/fvSolution PIMPLE): extra passes of the pEqn's
+                                      // non-orthogonal corrector loop (pEqn.H:51-62)
   };
   n = (int)(sizeof(d) / sizeof(d[0]));
   return d;
@@ -339,6 +341,12 @@ struct Ctx {
   DevBuf<double> md, bdv;        // mesh_distance [3][Fs], boundary delta [3][B] (dfmi_init_boundary_delta)
   bool have_bdelta = false;
   Schemes sch;
+  // laplacian scheme (dfmi_set_scheme "laplacian"): LAP_ORTHOGONAL reads dc / bdc as the caller gave them;
+  // the other two read the non-orthogonal delta coefficients (fields nonorth_delta_coeffs / boundary_nonorth_delta_coeffs,
+  // formed on the device by nonorth_setup), LAP_CORRECTED adds the explicit term from the correction vectors
+  // (nonorth_corr [3][Fs] / boundary_nonorth_corr [3][B]). The pointers are those fields' buffers (nullptr: orthogonal)
+  int lap = 0;
+  const double *no_dc = nullptr, *no_bdc = nullptr, *no_k = nullptr, *no_bk = nullptr;
   DevBuf<int> conv_list, conv_nlist;   // faces whose div(phi,Yi_h) limiter needs gradients (k_conv_w_check)
   // per-field patch types (host, per patch) and per-slot device copies
   std::map<std::string, std::vector<int>> ptype;
@@ -439,7 +447,8 @@ struct Ctx {
     m.C = C; m.F = Fs; m.B = B; m.S = S; m.fslot = fslot ? 1 : 0;
     m.own = own; m.nei = nei; m.ownStart = ownStart; m.nbrStart = nbrStart; m.nbrFace = nbrFace;
     m.cbStart = cbStart; m.cbSlot = cbSlot; m.bfc = bfc; m.partner = partner; m.sprim = sprim;
-    m.Sf = Sf; m.magSf = magSf; m.w = w; m.dc = dc; m.V = V; m.bSf = bSf; m.bmagSf = bmagSf; m.bw = bw; m.bdc = bdc;
+    m.Sf = Sf; m.magSf = magSf; m.w = w; m.V = V; m.bSf = bSf; m.bmagSf = bmagSf; m.bw = bw;
+    m.dc = lap ? no_dc : dc.p; m.bdc = lap ? no_bdc : bdc.p;
     m.ecol = ell.col; m.esrc = ell.src; m.W = ell.ready ? ell.W : 0;
     m.rdt = rdt;
     m.trav = trav.n ? trav.p : nullptr;
@@ -543,6 +552,15 @@ void turbulence_correct(Ctx& x);
 // slot from the slot's own values, from the fields as they stand (after the rhoEqn, before the three assemblies);
 // the first call in LES mode also zeroes the fields of the dropped terms. Throws when nut is not valid.
 void les_effective(Ctx& x);
+// laplacian schemes. nonorth_setup: the non-orthogonal delta coefficients and correction vectors from Sf,
+// mesh_distance and the patch deltas (surfaceInterpolation::makeNonOrthDeltaCoeffs / makeNonOrthCorrectionVectors).
+// nonorth_p_correct: the pEqn's explicit term from the current p / boundary_p -- source = base + div of the face flux
+// correction, which is kept for nonorth_p_flux (phi -= it on internal faces and coupled slots after p_post_solve).
+enum { LAP_ORTHOGONAL = 0, LAP_UNCORRECTED = 1, LAP_CORRECTED = 2 };
+void nonorth_setup(Ctx& x);
+void nonorth_p_base(Ctx& x);
+void nonorth_p_correct(Ctx& x);
+void nonorth_p_flux(Ctx& x);
 void courant_post(Ctx& x);   // queues the Courant-number reduction and its record (Ctx::co), no synchronisation
 void zero_d_step(Ctx& x, double dt);   // df0DFoam loop body for every cell
 void thermo_rho_from_psi(Ctx& x);

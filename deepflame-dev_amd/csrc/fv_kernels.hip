@@ -2160,6 +2160,209 @@ __global__ void __launch_bounds__(TPB) k_e_assemble(MeshView m, const int8_t* __
   });
 }
 
+// ------------------------------------------------------------------ non-orthogonal laplacians
+// surfaceInterpolation::makeNonOrthDeltaCoeffs / makeNonOrthCorrectionVectors per face of the face storage, from the
+// arrays the context holds (Sf, |Sf|, d = mesh_distance), in Mesh.nonorth_geometry's operation order:
+//   n = Sf / |Sf|;  nd = (n_x d_x + n_y d_y) + n_z d_z;  |d| = sqrt((d_x d_x + d_y d_y) + d_z d_z)
+//   nonOrthDeltaCoeffs = 1 / max(nd, 0.05 |d|);  k = n - d nonOrthDeltaCoeffs
+__device__ __forceinline__ void nonorth_face(const double (&s)[3], double ms, const double (&d)[3], double& dc, double (&k)[3]) {
+  const double n0 = s[0] / ms, n1 = s[1] / ms, n2 = s[2] / ms;
+  const double nd = (n0 * d[0] + n1 * d[1]) + n2 * d[2];
+  const double dm = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+  dc = 1.0 / fmax(nd, 0.05 * dm);
+  k[0] = n0 - d[0] * dc; k[1] = n1 - d[1] * dc; k[2] = n2 - d[2] * dc;
+}
+__global__ void k_nonorth_geom_face(MeshView m, double* __restrict__ ndc, double* __restrict__ nk) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= m.F) return;
+  const long F = m.F;
+  double dc = 0.0, k[3] = {0.0, 0.0, 0.0};
+  if (m.own[f] >= 0) {   // padding slots of the owner-slot storage stay zero
+    const double s[3] = {m.Sf[f], m.Sf[F + f], m.Sf[2 * F + f]}, d[3] = {m.md[f], m.md[F + f], m.md[2 * F + f]};
+    nonorth_face(s, m.magSf[f], d, dc, k);
+  }
+  ndc[f] = dc;
+  nk[f] = k[0]; nk[F + f] = k[1]; nk[2 * F + f] = k[2];
+}
+// boundary slots: coupled slots (cyclic, processor, processorCyclic; both halves of a processor patch) by the same
+// formulas from the patch delta; every other slot keeps its deltaCoeffs and has k = 0 (fvPatchField::gradientCoeffs
+// reads patch().deltaCoeffs())
+__global__ void k_nonorth_geom_slot(MeshView m, const int8_t* __restrict__ ty, const double* __restrict__ bdc0,
+                                    double* __restrict__ nbdc, double* __restrict__ nbk) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= m.B) return;
+  const long B = m.B;
+  double dc = bdc0[b], k[3] = {0.0, 0.0, 0.0};
+  if (bc_coupled(ty[b])) {
+    const double s[3] = {m.bSf[b], m.bSf[B + b], m.bSf[2 * B + b]}, d[3] = {m.bdv[b], m.bdv[B + b], m.bdv[2 * B + b]};
+    nonorth_face(s, m.bmagSf[b], d, dc, k);
+  }
+  nbdc[b] = dc;
+  nbk[b] = k[0]; nbk[B + b] = k[1]; nbk[2 * B + b] = k[2];
+}
+
+// The explicit part of a corrected laplacian (correctedSnGrad::correction, gaussLaplacianScheme::fvmLaplacian):
+//   fvm.source() -= V div(gamma_f |Sf| (k . (grad phi)_f)),  every laplacian entering its equation with a minus,
+// as one per-cell gather over NC fields that share the walk (U's three components, a chunk of species, he, p). The
+// cell's own gradients and diffusivities sit in registers; each face gathers the other cell's. Per face, in the
+// sequential face order (each_face), then per coupled slot of the cell in slot order:
+//   g_d    = interp_f(w, g_P,d, g_N,d)                        d = x, y, z (owner first; slots: interp_b(bw, own, other))
+//   corr_f = (k_x g_x + k_y g_y) + k_z g_z
+//   flux_f = (gamma_f |Sf|) corr_f                            gamma_f = interp_f(w, gamma_P, gamma_N), or the face field
+//   acc   += flux_f (owner) / acc -= flux_f (neighbour) / acc += flux_b (slot)
+// then source[c] = source[c] + acc: one accumulator per field, no atomics. k = 0 on non-coupled slots: they add nothing.
+// A coupled slot's other cell is the cyclic partner cell, or (processor slots) the exchanged copies bg / bgam.
+// Gradient component d of field k of cell c: g[(k gk + d gd) C + c] (k_grad_cells: gk = 3, gd = 1; k_u_grad's gout:
+// gk = 1, gd = 3), slots likewise with B.
+enum { NO_SHARED = 0, NO_SPECIES = 1, NO_FACE = 2 };
+struct NoArgs {
+  const double *nk, *bnk;       // correction vectors [3][Fs], [3][B]
+  const double *g, *bg;         // cell gradients and their processor-slot copies
+  int gk, gd;
+  // NO_SHARED: one cell diffusivity for the NC fields (mu / muEff, alpha / alphaEff). NO_SPECIES: field k's own,
+  // gam + (s0 + k) C (rhoD), plus `add` where set (LES: mut / Sct). NO_FACE: a face field (rhorAUf) and its slots
+  const double *gam, *bgam, *add, *badd;
+  double *src, *src2;           // sources [NC][C] the term is added to (src2: U's source_solve; nullptr: none)
+  // NO_SPECIES: first species of the chunk, species count, inert species (no equation); the solver rows' rhs
+  // [S - 1][Ce] at the row's position (nullptr: none); diffAlphaD's own laplacian(alpha hai_i, Y_i) on the same walk:
+  // dAD[c] = dAD[c] + acc2_k / V for the chunk's species in order (nullptr: LES, the term is dropped)
+  int s0, S, inert;
+  long Ce;
+  double* rhs;
+  const double *alpha, *balpha, *hai, *bhai;
+  double* dAD;
+  // NO_FACE: source = base + acc (the pEqn loop re-forms it every pass); the face flux correction of the owned faces and
+  // of the coupled slots (pEqn.flux()'s faceFluxCorrectionPtr)
+  const double* base;
+  double *fcorr, *bfcorr;
+};
+template <int NC, int WT, int MODE>
+__global__ void __launch_bounds__(TPB) k_nonorth_corr(MeshView m, const int8_t* __restrict__ ty, NoArgs a) {
+  const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
+  if (c >= m.C) return;
+  const long C = m.C, F = m.F, B = m.B;
+  const bool dad = MODE == NO_SPECIES && a.dAD != nullptr;
+  double gc[NC][3], gamc[NC], ahc[NC], acc[NC], acc2[NC];
+  const double addc = (MODE == NO_SPECIES && a.add) ? a.add[c] : 0.0;
+  const double alc = dad ? a.alpha[c] : 0.0;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    acc[k] = 0.0; acc2[k] = 0.0; ahc[k] = 0.0; gamc[k] = 0.0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) gc[k][d] = a.g[(long)(k * a.gk + d * a.gd) * C + c];
+    if constexpr (MODE == NO_SHARED) gamc[k] = a.gam[c];
+    if constexpr (MODE == NO_SPECIES) {
+      gamc[k] = a.gam[(long)(a.s0 + k) * C + c];
+      if (a.add) gamc[k] = gamc[k] + addc;
+      if (dad) ahc[k] = alc * a.hai[(long)(a.s0 + k) * C + c];
+    }
+  }
+  each_face<WT>(m, c, [&](int f, int o2, bool own) {
+    const double w = m.w[f], ms = m.magSf[f];
+    const double k0 = a.nk[f], k1 = a.nk[F + f], k2 = a.nk[2 * F + f];
+    auto fi = [&](double vc, double vn) { return own ? interp_f(w, vc, vn) : interp_f(w, vn, vc); };
+    double gsh = 0.0, addn = 0.0, aln = 0.0;
+    if constexpr (MODE == NO_SHARED) gsh = fi(gamc[0], a.gam[o2]);
+    if constexpr (MODE == NO_FACE) gsh = a.gam[f];
+    if constexpr (MODE == NO_SPECIES) { if (a.add) addn = a.add[o2]; if (dad) aln = a.alpha[o2]; }
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      const double g0 = fi(gc[k][0], a.g[(long)(k * a.gk) * C + o2]);
+      const double g1 = fi(gc[k][1], a.g[(long)(k * a.gk + a.gd) * C + o2]);
+      const double g2 = fi(gc[k][2], a.g[(long)(k * a.gk + 2 * a.gd) * C + o2]);
+      const double corr = (k0 * g0 + k1 * g1) + k2 * g2;
+      double gf = gsh;
+      if constexpr (MODE == NO_SPECIES) {
+        double gn = a.gam[(long)(a.s0 + k) * C + o2];
+        if (a.add) gn = gn + addn;
+        gf = fi(gamc[k], gn);
+      }
+      const double fl = (gf * ms) * corr;
+      if (own) acc[k] += fl; else acc[k] -= fl;
+      if constexpr (MODE == NO_FACE) { if (own) a.fcorr[f] = fl; }
+      if constexpr (MODE == NO_SPECIES) {
+        if (dad) {
+          const double fl2 = (fi(ahc[k], aln * a.hai[(long)(a.s0 + k) * C + o2]) * ms) * corr;
+          if (own) acc2[k] += fl2; else acc2[k] -= fl2;
+        }
+      }
+    }
+  });
+  each_slot(m, ty, c, [&](int b, int t) {
+    if (!bc_coupled(t)) return;
+    const int pc = m.partner[b];
+    const double bw = m.bw[b], ms = m.bmagSf[b];
+    const double k0 = a.bnk[b], k1 = a.bnk[B + b], k2 = a.bnk[2 * B + b];
+    double gsh = 0.0;
+    if constexpr (MODE == NO_SHARED) gsh = interp_b(bw, gamc[0], pc >= 0 ? a.gam[pc] : a.bgam[b]);
+    if constexpr (MODE == NO_FACE) gsh = a.bgam[b];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      double gg[3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const long q = k * a.gk + d * a.gd;
+        gg[d] = interp_b(bw, gc[k][d], pc >= 0 ? a.g[q * C + pc] : a.bg[q * B + b]);
+      }
+      const double corr = (k0 * gg[0] + k1 * gg[1]) + k2 * gg[2];
+      double gf = gsh;
+      if constexpr (MODE == NO_SPECIES) {
+        const long s = a.s0 + k;
+        double gn = pc >= 0 ? a.gam[s * C + pc] : a.bgam[s * B + b];
+        if (a.add) gn = gn + (pc >= 0 ? a.add[pc] : a.badd[b]);
+        gf = interp_b(bw, gamc[k], gn);
+      }
+      const double fl = (gf * ms) * corr;
+      acc[k] += fl;
+      if constexpr (MODE == NO_FACE) a.bfcorr[b] = fl;
+      if constexpr (MODE == NO_SPECIES) {
+        if (dad) {
+          const long s = a.s0 + k;
+          const double an = pc >= 0 ? a.alpha[pc] * a.hai[s * C + pc] : a.balpha[b] * a.bhai[s * B + b];
+          acc2[k] += (interp_b(bw, ahc[k], an) * ms) * corr;
+        }
+      }
+    }
+  });
+  if constexpr (MODE == NO_FACE) {
+    a.src[c] = a.base[c] + acc[0];
+  } else if constexpr (MODE == NO_SHARED) {
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      a.src[k * C + c] = a.src[k * C + c] + acc[k];
+      if (a.src2) a.src2[k * C + c] = a.src2[k * C + c] + acc[k];
+    }
+  } else {
+    const int pr = m.eopos ? m.eopos[c] : c;   // the solver row of c (even-odd layout)
+    const double vol = m.V[c];
+    double dd = dad ? a.dAD[c] : 0.0;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      const int s = a.s0 + k;
+      if (dad) dd = dd + acc2[k] / vol;
+      if (s == a.inert) continue;
+      if (a.src) a.src[(long)s * C + c] = a.src[(long)s * C + c] + acc[k];
+      if (a.rhs) {
+        const long ss = s < a.inert ? s : s - 1;
+        a.rhs[ss * a.Ce + pr] = a.rhs[ss * a.Ce + pr] + acc[k];
+      }
+    }
+    if (dad) a.dAD[c] = dd;
+  }
+}
+// phi -= the face flux correction (internal faces of the face storage; coupled primary slots)
+__global__ void k_nonorth_flux_face(MeshView m, const double* __restrict__ fcorr, double* __restrict__ phi) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= m.F || m.own[f] < 0) return;
+  phi[f] = phi[f] - fcorr[f];
+}
+__global__ void k_nonorth_flux_slot(MeshView m, const int8_t* __restrict__ ty, const double* __restrict__ bfcorr,
+                                    double* __restrict__ bphi) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= m.B || !m.sprim[b] || !bc_coupled(ty[b])) return;
+  bphi[b] = bphi[b] - bfcorr[b];
+}
+
 // ------------------------------------------------------------------ df0DFoam species update
 // YEqn.H of df0DFoam (applications/solvers/df0DFoam/YEqn.H): fvm::ddt(rho, Yi) == RR_i per cell (no
 // transport), solved exactly: Y_i = (rdt rho_old Y_i V + V RR_i) / (rdt rho V); Yi.max(0); inert = 1 - sum.
@@ -2320,13 +2523,20 @@ static void scheme_checks(Ctx& x, bool limited) {
   DFMI_CHECK(!limited || x.have_md, "limited schemes need mesh_distance (dfmi_init_constant_fields_internal)");
 }
 
+// the explicit part of the corrected laplacians (LAP_CORRECTED), added to the sources the assembly kernels wrote
+static void nonorth_u(Ctx& x);
+static void nonorth_e(Ctx& x);
+static void nonorth_y(Ctx& x, double* src, double* rhs, long Ce);
+
 void u_assemble(Ctx& x) {
   Matrix& A = x.mU;
   const bool llv = x.sch.U == SCH_LLV;
-  double* gout = llv ? scheme_buf(x, "gradU", x.C, 9) : x.fields.count("dbg_gradU") ? x.f("dbg_gradU") : nullptr;
+  double* gout = llv || x.lap == LAP_CORRECTED ? scheme_buf(x, "gradU", x.C, 9) : x.fields.count("dbg_gradU") ? x.f("dbg_gradU") : nullptr;
   LAUNCH_W(k_u_grad, x.C, x.view(), x.st("U"), x.f("U"), x.f("boundary_U"), x.visc(false), x.visc(true),
          x.f("tauU"), x.f("boundary_tauU"), gout);
   halo_fields(x, {"tauU"});   // fvc_grad_vector_correctBC_processor (dfMatrixOpBase.cu:1366-1389)
+  if (!llv && x.lap == LAP_CORRECTED && x.fields.count("dbg_gradU"))
+    DFMI_HIP(hipMemcpyAsync(x.f("dbg_gradU"), gout, 9 * sizeof(double) * x.C, hipMemcpyDeviceToDevice, x.stream));
   if (llv) {   // div(phi,U) limitedLinearV weights from this grad(U)
     scheme_checks(x, true);
     for (int p = 0; p < x.P; ++p)   // dfmi_set_scheme refuses it too; checked again here, where it is launched
@@ -2343,6 +2553,7 @@ void u_assemble(Ctx& x) {
            x.f("boundary_U"), x.f("phi"), x.f("boundary_phi"), x.visc(false), x.visc(true), x.f("p"),
            x.f("boundary_p"), x.f("tauU"), x.f("boundary_tauU"), A.lower.p, A.upper.p, A.diag.p, A.source.p,
            A.source_solve.p, A.ic.p, A.bc.p, x.f("rAU"), mixbc(x, "U"), x.sch_w(6), x.sch_w(7));
+  if (x.lap == LAP_CORRECTED) nonorth_u(x);
   k_bc_correct(x, "extrapolated", x.f("rAU"), x.f("boundary_rAU"), 1);
   halo_fields(x, {"rAU"});
 }
@@ -2618,6 +2829,7 @@ void y_assemble(Ctx& x) {
                        x.f("boundary_rhoD"), x.f("RR"), x.f("rho"), x.f("rho_old"), x.f("phi"), x.f("boundary_phi"),
                        x.f("phiUc"), x.f("boundary_phiUc"), A.lower.p, A.upper.p, A.diag.p, A.source.p, A.ic.p, A.bc.p, mixbc(x, "Y"), x.sch_w(0), x.sch_w(1)))
 #undef CALL
+  if (x.lap == LAP_CORRECTED) nonorth_y(x, A.source.p, nullptr, 0);
 }
 
 void y_assemble_ell(Ctx& x, int W, long Ce, double* val, double* dS, double* rhs) {
@@ -2641,6 +2853,7 @@ void y_assemble_ell(Ctx& x, int W, long Ce, double* val, double* dS, double* rhs
   DFMI_SWITCH_S(x.S, CALL, GEN(8))
 #undef GEN
 #undef CALL
+  if (x.lap == LAP_CORRECTED) nonorth_y(x, nullptr, rhs, Ce);
 }
 
 void y_post_solve(Ctx& x) {
@@ -2666,11 +2879,121 @@ void e_assemble_back(Ctx& x) {
          x.cond(true), x.f("hDiffCorrFlux"), x.f("boundary_hDiffCorrFlux"), x.f("dpdt"), x.f("diffAlphaD"),
          eg, A.lower.p, A.upper.p, A.diag.p, A.source.p, A.ic.p, A.bc.p, x.sch_w(0), x.sch_w(1), x.sch_w(2),
          x.sch_w(3), x.sch_w(4), x.sch_w(5));
+  if (x.lap == LAP_CORRECTED) nonorth_e(x);
 }
 void e_assemble(Ctx& x) {
   e_assemble_front(x);
   e_assemble_back(x);
 }
+
+// ---- non-orthogonal laplacians (dfmi_set_scheme "laplacian")
+void nonorth_setup(Ctx& x) {
+  double* ndc = scheme_buf(x, "nonorth_delta_coeffs", x.Fs, 1, true);
+  double* nk = scheme_buf(x, "nonorth_corr", x.Fs, 3, true);
+  double* nbdc = scheme_buf(x, "boundary_nonorth_delta_coeffs", x.B, 1);
+  double* nbk = scheme_buf(x, "boundary_nonorth_corr", x.B, 3);
+  const int lap = x.lap;
+  x.lap = LAP_ORTHOGONAL;   // the view with the caller's deltaCoeffs: the slots that are not coupled copy them
+  const MeshView m = x.view();
+  x.lap = lap;
+  LAUNCH(k_nonorth_geom_face, x.Fs, m, ndc, nk);
+  LAUNCH(k_nonorth_geom_slot, x.B, m, x.st("calculated"), x.bdc.p, nbdc, nbk);
+  x.no_dc = ndc; x.no_bdc = nbdc; x.no_k = nk; x.no_bk = nbk;
+}
+#define LAUNCH_NO(NC, MODE, ty, a) \
+  do { if (face_hex(x)) LAUNCH((k_nonorth_corr<NC, -1, MODE>), x.C, m, ty, a); \
+       else if (face_rows(x)) LAUNCH((k_nonorth_corr<NC, 6, MODE>), x.C, m, ty, a); \
+       else LAUNCH((k_nonorth_corr<NC, 0, MODE>), x.C, m, ty, a); } while (0)
+#define LAUNCH_GRAD(NC, ty, vf, bvf, g) \
+  do { if (face_hex(x)) LAUNCH((k_grad_cells<NC, -1>), x.C, m, ty, vf, bvf, g); \
+       else if (face_rows(x)) LAUNCH((k_grad_cells<NC, 6>), x.C, m, ty, vf, bvf, g); \
+       else LAUNCH((k_grad_cells<NC, 0>), x.C, m, ty, vf, bvf, g); } while (0)
+static NoArgs no_args(Ctx& x) {
+  NoArgs a{};
+  a.nk = x.no_k; a.bnk = x.no_bk; a.gk = 3; a.gd = 1; a.inert = -1;
+  return a;
+}
+// UEqn: - fvm::laplacian(mu, U), the three components on one walk from k_u_grad's gradient (u_assemble's gout)
+static void nonorth_u(Ctx& x) {
+  const MeshView m = x.view();
+  scheme_buf(x, "boundary_gradU", x.B, 9);
+  halo_fields(x, {"gradU"});   // the neighbour cell's gradient on processor faces
+  NoArgs a = no_args(x);
+  a.g = x.f("gradU"); a.bg = x.f("boundary_gradU"); a.gk = 1; a.gd = 3;
+  a.gam = x.visc(false); a.bgam = x.visc(true);
+  a.src = x.mU.source.p; a.src2 = x.mU.source_solve.p;
+  LAUNCH_NO(3, NO_SHARED, x.st("U"), a);
+}
+// EEqn: - fvm::laplacian(alpha, he) from he / boundary_he as the assembly read them
+static void nonorth_e(Ctx& x) {
+  const MeshView m = x.view();
+  double* g = scheme_buf(x, "nonorth_grad", x.C, 3);
+  scheme_buf(x, "boundary_nonorth_grad", x.B, 3);
+  LAUNCH_GRAD(1, x.st("he"), x.f("he"), x.f("boundary_he"), g);
+  halo_fields(x, {"nonorth_grad"});
+  NoArgs a = no_args(x);
+  a.g = g; a.bg = x.f("boundary_nonorth_grad");
+  a.gam = x.cond(false); a.bgam = x.cond(true);
+  a.src = x.mE.source.p;
+  LAUNCH_NO(1, NO_SHARED, x.st("he"), a);
+}
+// YEqn: laplacian(rhoD_i, Yi) on the right-hand side, into the LDU source (src) or the solver rows' rhs, and
+// diffAlphaD's fvc::laplacian(alpha hai_i, Yi) on the same walk (y_prep wrote its orthogonal part just before: every
+// YEqn assembly follows a y_prep). Species in chunks of 4 (then singly), so the gradients take [12][C] at any S.
+static void nonorth_y(Ctx& x, double* src, double* rhs, long Ce) {
+  const MeshView m = x.view();
+  double* g = scheme_buf(x, "nonorth_gradY", x.C, 12);
+  scheme_buf(x, "boundary_nonorth_gradY", x.B, 12);
+  NoArgs a = no_args(x);
+  a.g = g; a.bg = x.f("boundary_nonorth_gradY");
+  a.gam = x.f("rhoD"); a.bgam = x.f("boundary_rhoD"); a.add = x.mut_sct(false); a.badd = x.mut_sct(true);
+  a.src = src; a.rhs = rhs; a.Ce = Ce; a.S = x.S; a.inert = x.inert;
+  if (!x.les.model) {   // LES drops diffAlphaD (y_prep)
+    a.alpha = x.f("alpha"); a.balpha = x.f("boundary_alpha"); a.hai = x.f("hai"); a.bhai = x.f("boundary_hai");
+    a.dAD = x.f("diffAlphaD");
+  }
+  const int8_t* ty = x.st("Y");
+  for (int s0 = 0; s0 < x.S;) {
+    const int n = x.S - s0 >= 4 ? 4 : 1;
+    const double *vf = x.f("Y") + (long)s0 * x.C, *bvf = x.f("boundary_Y") + (long)s0 * x.B;
+    a.s0 = s0;
+    if (n == 4) LAUNCH_GRAD(4, ty, vf, bvf, g); else LAUNCH_GRAD(1, ty, vf, bvf, g);
+    if (halo_active(x)) {   // the neighbour cells' gradients on processor faces: only the components this chunk formed
+      CommTag _ct(x, "fields nonorth_gradY");
+      const HaloItem it{g, x.f("boundary_nonorth_gradY"), 3 * n, (long)x.C, (long)x.B, true};
+      halo_update(x, &it, 1);
+    }
+    if (n == 4) LAUNCH_NO(4, NO_SPECIES, ty, a); else LAUNCH_NO(1, NO_SPECIES, ty, a);
+    s0 += n;
+  }
+}
+// pEqn (do_p's non-orthogonal corrector loop): the source k_p_cell wrote is kept as the base; every pass forms
+// grad(p) from p / boundary_p as they stand and source = base + the divergence of the face flux correction
+void nonorth_p_base(Ctx& x) {
+  double* base = scheme_buf(x, "nonorth_p_base", x.C, 1);
+  DFMI_HIP(hipMemcpyAsync(base, x.mP.source.p, sizeof(double) * x.C, hipMemcpyDeviceToDevice, x.stream));
+}
+void nonorth_p_correct(Ctx& x) {
+  const MeshView m = x.view();
+  double* g = scheme_buf(x, "nonorth_grad", x.C, 3);
+  scheme_buf(x, "boundary_nonorth_grad", x.B, 3);
+  LAUNCH_GRAD(1, x.st("p"), x.f("p"), x.f("boundary_p"), g);
+  halo_fields(x, {"nonorth_grad"});
+  NoArgs a = no_args(x);
+  a.g = g; a.bg = x.f("boundary_nonorth_grad");
+  a.gam = x.f("rhorAUf"); a.bgam = x.f("boundary_rhorAUf");
+  a.src = x.mP.source.p; a.base = x.f("nonorth_p_base");
+  a.fcorr = scheme_buf(x, "nonorth_p_flux", x.Fs, 1, true); a.bfcorr = scheme_buf(x, "boundary_nonorth_p_flux", x.B, 1);
+  LAUNCH_NO(1, NO_FACE, x.st("p"), a);
+}
+// phi = phiHbyA + pEqn.flux() includes the face flux correction of the last pass (after p_post_solve wrote phi)
+void nonorth_p_flux(Ctx& x) {
+  const MeshView m = x.view();
+  LAUNCH(k_nonorth_flux_face, x.Fs, m, x.f("nonorth_p_flux"), x.f("phi"));
+  LAUNCH(k_nonorth_flux_slot, x.B, m, x.st("p"), x.f("boundary_nonorth_p_flux"), x.f("boundary_phi"));
+}
+#undef LAUNCH_GRAD
+#undef LAUNCH_NO
 
 void e_post_solve(Ctx& x) {
   k_bc_correct(x, "he", x.f("he"), x.f("boundary_he"), 1);

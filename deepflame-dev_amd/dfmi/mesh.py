@@ -145,6 +145,31 @@ class Mesh:
             out += [dv] * reps
         return np.concatenate(out) if out else np.zeros((0, 3))
 
+    def nonorth_geometry(self, dtype=np.float64):
+        """surfaceInterpolation::makeNonOrthDeltaCoeffs / makeNonOrthCorrectionVectors (OpenFOAM-7) in the library's
+        operation order (csrc/fv_kernels.hip nonorth_face): (nonorth_delta_coeffs [F], nonorth_corr [F,3],
+        boundary_nonorth_delta_coeffs [B], boundary_nonorth_corr [B,3]). Coupled slots (cyclic, processor,
+        processorCyclic) use the patch delta; every other slot keeps its deltaCoeffs and has k = 0."""
+        def form(sf, mag, d):
+            sf, mag, d = (np.asarray(a, dtype=dtype) for a in (sf, mag, d))
+            n = sf / mag[:, None]
+            nd = (n[:, 0] * d[:, 0] + n[:, 1] * d[:, 1]) + n[:, 2] * d[:, 2]
+            dm = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+            dc = 1.0 / np.maximum(nd, dtype(0.05) * dm)
+            return dc, n - d * dc[:, None]
+        dc, k = form(self.sf, self.mag_sf, self.mesh_distance)
+        bsf, bmag, bdc, _, _ = self.boundary_arrays()
+        bdelta = self.boundary_delta()
+        bdc = np.array(bdc, dtype=dtype)
+        bk = np.zeros((bdc.size, 3), dtype=dtype)
+        off = 0
+        for p in self.patches:
+            if p.kind in ("cyclic", "processor", "processorCyclic") and p.size:
+                s = slice(off, off + p.slots)
+                bdc[s], bk[s] = form(bsf[s], bmag[s], bdelta[s])
+            off += p.slots
+        return dc, k, bdc, bk
+
     def proc_rows_cols(self):
         """procRows/procCols for processor interfaces (createGPUSolver.H:205-243)."""
         rows, cols = [], []

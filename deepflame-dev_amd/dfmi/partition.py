@@ -182,7 +182,7 @@ def decompose(m: Mesh, part: np.ndarray) -> list:
             else:
                 sel = np.flatnonzero(part[p.face_cells] == r)
             np_ = Patch(p.name, p.kind, local[p.face_cells[sel]].astype(np.int32), p.sf[sel], p.mag_sf[sel],
-                        p.weight[sel], p.delta_coeffs[sel])
+                        p.weight[sel], p.delta_coeffs[sel], delta=None if p.delta is None else np.asarray(p.delta)[sel])
             np_.neighbour_patch = p.neighbour_patch
             patches.append(np_)
         # processor patches: one per neighbour rank, faces in serial face order
@@ -197,7 +197,8 @@ def decompose(m: Mesh, part: np.ndarray) -> list:
             sgn = np.where(is_own, 1.0, -1.0)[:, None]
             w = np.where(is_own, m.weight[f], 1.0 - m.weight[f])
             p = Patch(f"procBoundary{r}to{q}", "processor", local[fc].astype(np.int32), m.sf[f] * sgn, m.mag_sf[f].copy(),
-                      w, m.delta_coeffs[f].copy(), peer_rank=q)
+                      w, m.delta_coeffs[f].copy(), peer_rank=q,
+                      delta=np.asarray(m.mesh_distance)[f] * sgn)   # processorFvPatch::delta: this side's cell to the other's
             p.nbr_cells_global = (offset[q] + local[oc]).astype(np.int32)
             patches.append(p)
         # processorCyclic: cyclic pairs across ranks, one patch per (peer, cyclic patch), pair order
@@ -209,7 +210,8 @@ def decompose(m: Mesh, part: np.ndarray) -> list:
             for q in sorted(set(part[q_p.face_cells[mine]].tolist())):
                 sel = mine[part[q_p.face_cells[mine]] == q]
                 pp = Patch(f"procBoundary{r}to{q}through{p.name}", "processorCyclic", local[p.face_cells[sel]].astype(np.int32),
-                           p.sf[sel], p.mag_sf[sel], p.weight[sel], p.delta_coeffs[sel], peer_rank=q)
+                           p.sf[sel], p.mag_sf[sel], p.weight[sel], p.delta_coeffs[sel], peer_rank=q,
+                           delta=None if p.delta is None else np.asarray(p.delta)[sel])
                 pp.nbr_cells_global = (offset[q] + local[q_p.face_cells[sel]]).astype(np.int32)
                 pp.refer_patch = p.name
                 patches.append(pp)

@@ -83,12 +83,97 @@ def dict_entries(txt: str) -> list:
     return out
 
 
+LAPLACIAN = "laplacian"
+LAPLACIAN_SCHEMES = ("orthogonal", "uncorrected", "corrected")
+
+
+def parse_laplacian(scheme: str) -> str:
+    """'Gauss linear corrected' -> 'corrected': the snGrad part of a laplacianSchemes entry. The library runs one
+    laplacian scheme for the U, Yi, he and p equations, Gauss with linear interpolation of the diffusivity;
+    'limited <psi>' and every other snGrad scheme are refused by name."""
+    tok = scheme.split()
+    if tok and tok[0] == "Gauss":
+        tok = tok[1:]
+    if tok and tok[0] == "linear":
+        tok = tok[1:]
+    if not tok:
+        raise ValueError("laplacian: empty scheme")
+    if tok[0] == "limited":
+        raise ValueError(f"laplacian: the snGrad scheme 'limited' is not supported ({scheme!r})")
+    if tok[0] not in LAPLACIAN_SCHEMES:
+        raise ValueError(f"laplacian: unsupported scheme {scheme!r}; expected one of {LAPLACIAN_SCHEMES}")
+    if len(tok) != 1:
+        raise ValueError(f"laplacian: unexpected arguments in {scheme!r}")
+    return tok[0]
+
+
+def _block(txt: str, name: str):
+    """the text between the braces of the first-level dictionary `name` (nested braces kept), or None"""
+    import re
+    mo = re.search(r"(?<![\w()])" + re.escape(name) + r"\s*\{", txt)
+    if not mo:
+        return None
+    depth, i = 1, mo.end()
+    while i < len(txt) and depth:
+        depth += {"{": 1, "}": -1}.get(txt[i], 0)
+        i += 1
+    return txt[mo.end():i - 1]
+
+
 def read_fv_schemes(path: str) -> dict:
-    """the divSchemes entries of a case's system/fvSchemes for TERMS ({term: scheme})"""
+    """the entries of a case's system/fvSchemes that dfmi_set_scheme selects ({term: scheme}): the divSchemes entries
+    for TERMS, and 'laplacian' from laplacianSchemes { default ...; } when it is not the default 'orthogonal'. A per-term laplacian entry that differs from
+    the default (or per-term entries that differ from each other, without a default) is an error: the library runs
+    one laplacian scheme."""
     import re
     txt = open(path).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     txt = re.sub(r"//.*", "", txt)
-    mo = re.search(r"divSchemes\s*\{(.*?)\}", txt, re.S)
-    if not mo:
-        return {}
-    return {k: v for k, v in dict_entries(mo.group(1)) if k in TERMS}
+    out = {}
+    div = _block(txt, "divSchemes")
+    if div is not None:
+        out.update({k: v for k, v in dict_entries(div) if k in TERMS})
+    lap = _block(txt, "laplacianSchemes")
+    if lap is not None:
+        entries = dict_entries(lap)
+        default = [v for k, v in entries if k == "default"]
+        kinds = {k: parse_laplacian(v) for k, v in entries if k != "default"}
+        if default and default[-1].split()[0] != "none":
+            want = parse_laplacian(default[-1])
+        elif kinds:
+            want = next(iter(kinds.values()))
+        else:
+            want = None
+        for k, v in kinds.items():
+            if v != want:
+                raise ValueError(f"laplacianSchemes: {k} selects {v!r} but the other laplacians {want!r}; "
+                                 "one scheme serves every laplacian")
+        if want is not None and want != "orthogonal":   # the default is left out, as an absent block is
+            out[LAPLACIAN] = want
+    return out
+
+
+def read_fv_solution(path: str) -> dict:
+    """the PIMPLE block of a case's system/fvSolution: {'nCorrectors': int (dfmi_time_step's n_corr),
+    'nNonOrthogonalCorrectors': int (option p.n_nonorth)}, OpenFOAM's defaults (1, 0) where an entry is absent.
+    nOuterCorrectors other than 1 is refused: dfmi_time_step is one outer iteration."""
+    import re
+    txt = open(path).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"//.*", "", txt)
+    blk = _block(txt, "PIMPLE")
+    if blk is None:
+        raise ValueError(f"{path}: no PIMPLE dictionary")
+    e = dict(dict_entries(blk))
+
+    def count(key, default, least):
+        try:
+            v = int(e.get(key, default))
+        except ValueError:
+            raise ValueError(f"PIMPLE: {key} must be an integer, got {e[key]!r}") from None
+        if v < least:
+            raise ValueError(f"PIMPLE: {key} must be >= {least}, got {v}")
+        return v
+    if count("nOuterCorrectors", 1, 1) != 1:
+        raise ValueError("PIMPLE: nOuterCorrectors other than 1 is not supported (one outer iteration per time step)")
+    return {"nCorrectors": count("nCorrectors", 1, 0), "nNonOrthogonalCorrectors": count("nNonOrthogonalCorrectors", 0, 0)}

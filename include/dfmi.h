@@ -96,7 +96,33 @@ int dfmi_init_boundary_delta(dfmi_ctx* ctx, const double* boundary_delta);
  * patches) every term's schemes are supported except div(phi,U) limitedLinearV, which is an error (here
  * and again when the UEqn is assembled). Limited schemes need the mesh_distance argument of
  * dfmi_init_constant_fields_internal (a NULL there makes them an error at the first assembly) and, on
- * meshes with coupled patches, dfmi_init_boundary_delta. */
+ * meshes with coupled patches, dfmi_init_boundary_delta.
+ *
+ * Laplacian scheme (system/fvSchemes laplacianSchemes { default ...; }): one more term,
+ *   "laplacian"           "orthogonal" (default) | "uncorrected" | "corrected"
+ * a leading "Gauss linear" is accepted ("Gauss linear corrected"); "limited <psi>" and every other snGrad scheme are
+ * refused by name. It serves the four laplacians: laplacian(mu | muEff, U), laplacian(rhoD_i (+ mut / Sct), Yi) with
+ * diffAlphaD's laplacian(alpha hai_i, Yi), laplacian(alpha | alphaEff, he) and laplacian(rhorAUf, p).
+ *   orthogonal   the caller's delta_coeffs (1 / |d|) and nothing else: the reference's box cases
+ *   uncorrected  OpenFOAM-7's nonOrthDeltaCoeffs = 1 / max(n.d, 0.05 |d|) (n = Sf / |Sf|, d = mesh_distance; on cyclic,
+ *                processor and processorCyclic slots d = the patch delta of dfmi_init_boundary_delta) wherever the
+ *                assemblies read delta_coeffs; non-coupled patches keep boundary_delta_coeffs
+ *   corrected    the same implicit part, and the explicit term of correctedSnGrad: per equation
+ *                source += sum over the cell's faces of gamma_f |Sf| (k . (grad phi)_f), outward, with
+ *                k = n - d nonOrthDeltaCoeffs (0 on non-coupled patches) and (grad phi)_f the linear interpolate of the
+ *                cell-centred Gauss linear gradient (U: source, source_solve and so HbyA; Yi: the LDU source and the
+ *                solver rows' rhs; diffAlphaD takes its own term; p: see the option p.n_nonorth below)
+ * The library forms both arrays on the device when a scheme other than orthogonal is first selected; dfmi_get_field
+ * returns them in OpenFOAM face order as "nonorth_delta_coeffs" [F], "nonorth_corr" [F] x 3,
+ * "boundary_nonorth_delta_coeffs" [B] and "boundary_nonorth_corr" [B] x 3 (they cannot be set). Errors, each leaving
+ * the scheme in force: no mesh_distance was given; the mesh has coupled patches and dfmi_init_boundary_delta was not
+ * called; an unknown or limited scheme.
+ * Option p.n_nonorth (integer >= 0, default 0) is PIMPLE's nNonOrthogonalCorrectors: every pEqn assembles once and runs
+ * 1 + p.n_nonorth passes of { grad p from p / boundary_p as they stand; source = base + the divergence of the face flux
+ * correction; solve } (pEqn.H:51-62); phi = phiHbyA + pEqn.flux() includes the last pass's face flux correction on
+ * internal faces and coupled slots. With "corrected" the loop runs once even at p.n_nonorth = 0, with the correction
+ * from the incoming p; with the other two schemes and p.n_nonorth = 0 the pEqn is the one solve it always was.
+ * dfmi_time_step keeps its signature. The CPU-A baseline returns an error for every laplacian scheme but orthogonal. */
 int dfmi_set_scheme(dfmi_ctx* ctx, const char* term, const char* scheme);
 
 /* ---- cell renumbering (the role of OpenFOAM's renumberMesh; run once on the host before
@@ -230,7 +256,8 @@ int dfmi_hbm_copy_peak(dfmi_ctx* ctx, double gib, int reps, double* gbs);
 int dfmi_correct_boundary(dfmi_ctx* ctx, const char* field);
 
 /* ---- matrix inspection (the reference DEBUG_CHECK_LDU / compareResult path, dfYEqn.cu:566-572) */
-/* eqn in {"rho","U","Y","E","p","HbyA","Y_ell","Y_ell_ref"}: run that equation's assembly only (no solve) */
+/* eqn in {"rho","U","Y","E","p","HbyA","Y_ell","Y_ell_ref"}: run that equation's assembly only (no solve); under
+ * the laplacian scheme "corrected" the sources include the explicit term ("p": that of the corrector loop's first pass) */
 int dfmi_assemble(dfmi_ctx* ctx, const char* eqn);
 /* part in {"lower","upper","diag","source","source_solve","internal_coeffs","boundary_coeffs"} */
 int dfmi_get_matrix(dfmi_ctx* ctx, const char* eqn, const char* part, double* host, long count);
