@@ -98,6 +98,10 @@ struct Ctx {
   double rdt = 0, dt = 0;   // 1 / deltaT (bound to the restatement at every call) and deltaT as given (dfmi_set_delta_t)
   // LES (options les.*; include/dfmi.h dfmi_turbulence_correct): the model, its coefficients and whether nut belongs to
   // them, delta and U as they stand
+  // RAS (options ras.*): the keys and defaults of the HIP library, accepted and kept; ras.model != 0 is refused by name
+  std::map<std::string, double> ras = {{"ras.model", 0}, {"ras.Cmu", 0.09}, {"ras.C1", 1.44}, {"ras.C2", 1.92}, {"ras.C3", 0.0},
+                                       {"ras.sigmak", 1.0}, {"ras.sigmaEps", 1.3}, {"ras.kMin", 1e-15}, {"ras.epsilonMin", 1e-15},
+                                       {"ras.Prt", 1.0}, {"ras.Sct", 1.0}};
   struct Les { int model = 0; double Ck = 0.094, Ce = 1.048, Cw = 0.325, Prt = 1.0, Sct = 1.0; bool valid = false, have_delta = false; } les;
   bool step_courant = false;   // option step.courant: accepted for the callers that set it; the number is always computed on demand
   bool have_sizes = false, have_topo = false, have_geom = false, have_bgeom = false;
@@ -1280,6 +1284,18 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
       *slot = value;
       return;
     }
+    if (ctx && key && std::string(key).rfind("ras.", 0) == 0) {   // the keys of the HIP library; the model itself is its alone
+      const std::string k(key);
+      auto it = ctx->x.ras.find(k);
+      CHECK(it != ctx->x.ras.end(), "unknown option '" + k + "'");
+      if (k == "ras.model") {
+        CHECK(value == 0.0 || value == 1.0, "ras.model must be 0 (none) or 1 (kEpsilon)");
+        CHECK(value == 0.0, "ras.model = 1: CPU-A does not implement the k-epsilon model (the HIP library)");
+      } else if (k == "ras.C3") CHECK(value >= -1.79769313486231570e308 && value <= 1.79769313486231570e308, "ras.C3 must be finite");
+      else CHECK(value > 0 && value <= 1.79769313486231570e308, k + " must be positive and finite");
+      it->second = value;
+      return;
+    }
     throw Error(std::string("dfmi (CPU-A): option '") + key + "' is not configurable here");
   });
 }
@@ -1293,6 +1309,12 @@ int dfmi_get_option(dfmi_ctx* ctx, const char* key, double* value) {
       const double* slot = k == "les.Ck" ? &q.Ck : k == "les.Ce" ? &q.Ce : k == "les.Cw" ? &q.Cw : k == "les.Prt" ? &q.Prt : k == "les.Sct" ? &q.Sct : nullptr;
       CHECK(slot, "unknown option '" + k + "'");
       *value = *slot;
+      return;
+    }
+    if (ctx && key && value && std::string(key).rfind("ras.", 0) == 0) {
+      auto it = ctx->x.ras.find(key);
+      CHECK(it != ctx->x.ras.end(), std::string("unknown option '") + key + "'");
+      *value = it->second;
       return;
     }
     throw Error(std::string("dfmi (CPU-A): option '") + key + "' is not configurable here");

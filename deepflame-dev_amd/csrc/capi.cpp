@@ -95,6 +95,36 @@ void ensure_les_fields(Ctx& x) {
   alloc_field(x, "boundary_nut", x.B, 1, true);
 }
 
+// RAS k-epsilon (options ras.*): k, epsilon and their slots, the inletValue of both, G and divU, the solved (pre-bound)
+// copies bound() gathers from, the per-cell sources and diffusivity, and the scalar assembly's matrix. Allocated when
+// ras.model is first non-zero or one of these fields or their patch types is first touched: nothing in a laminar or LES
+// context.
+void ensure_ras_fields(Ctx& x) {
+  if (x.fields.count("epsilon")) return;
+  ensure_les_fields(x);
+  const long C = x.C, B = x.B;
+  for (auto n : {"k", "epsilon", "k_prebound", "epsilon_prebound", "ras_D"}) {
+    alloc_field(x, n, C, 1, false);
+    alloc_field(x, std::string("boundary_") + n, B, 1, true);
+  }
+  for (auto n : {"G", "divU", "ras_Su", "ras_Sp"}) alloc_field(x, n, C, 1, false);
+  alloc_field(x, "boundary_k_ref", B, 1, true);
+  alloc_field(x, "boundary_epsilon_ref", B, 1, true);
+  Matrix& A = x.mK;
+  A.nsys = 1;
+  A.lower.alloc((size_t)x.Fs); A.upper.alloc((size_t)x.Fs); A.diag.alloc((size_t)C); A.source.alloc((size_t)C);
+  A.ic.alloc((size_t)B); A.bc.alloc((size_t)B);
+  A.lower.zero(x.stream); A.upper.zero(x.stream); A.diag.zero(x.stream); A.source.zero(x.stream);
+  A.ic.zero(x.stream); A.bc.zero(x.stream);
+  for (auto e : {"k", "epsilon"}) if (!x.solver.count(e)) x.solver[e] = SolverCfg{20, 1e-5, 0.0};
+}
+bool ras_name(const std::string& n) {
+  static const char* names[] = {"k", "epsilon", "boundary_k", "boundary_epsilon", "G", "divU", "k_prebound", "epsilon_prebound",
+                                "boundary_k_prebound", "boundary_epsilon_prebound", "boundary_k_ref", "boundary_epsilon_ref"};
+  for (const char* s : names) if (n == s) return true;
+  return false;
+}
+
 // Build the deterministic gather topology from owner/neighbour and the boundary face cells.
 void build_boundary_topology(Ctx& x) {
   const int C = x.C, B = x.B;
@@ -363,6 +393,22 @@ void do_p(Ctx& x) {
             fuse);
   p_post_solve(x);
 }
+// kEpsilon::correct() (include/dfmi.h): G and divU, the epsilon equation, bound, the k equation with the new epsilon,
+// bound, correctNut(). Everything on the context stream: it runs after the pressure correctors, beside nothing.
+void ras_solve(Ctx& x, int keq) {
+  const char* nm = keq ? "k" : "epsilon";
+  Matrix& A = x.mK;
+  ras_assemble(x, keq);
+  solve_bicgstab(x, nm, 1, nullptr, A.lower, 0, A.upper, 0, A.diag, 0, A.source, 0, A.ic, A.bc, 0, nm, x.f(nm), 0, x.solver[nm]);
+  ras_post_solve(x, keq);
+}
+void ras_correct(Ctx& x) {
+  ensure_ras_fields(x);
+  ras_production(x);
+  ras_solve(x, 0);
+  ras_solve(x, 1);
+  ras_nut(x);
+}
 // step.hbya_early applies: the two-stream step on one rank (several ranks keep today's order: HbyA's field halo
 // stays behind the Y and E solves' exchanges)
 bool hbya_early(const Ctx& x) {
@@ -542,15 +588,18 @@ int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* patch_type
     Ctx& x = ctx->x;
     DFMI_CHECK(x.have_bgeom, "call dfmi_init_constant_fields_boundary first");
     std::string f(field);
-    static const char* ok[] = {"U", "p", "he", "K", "Y", "T", "rho", "nut"};
+    static const char* ok[] = {"U", "p", "he", "K", "Y", "T", "rho", "nut", "k", "epsilon"};
+    const bool ras = f == "k" || f == "epsilon";
     DFMI_CHECK(std::find_if(std::begin(ok), std::end(ok), [&](const char* s) { return f == s; }) != std::end(ok),
                "unknown patch-type field '" + f + "'");
     for (int p = 0; p < x.P; ++p) {
       const int t = patch_type[p];
       DFMI_CHECK(t >= 0 && t <= 12 && t != COUPLED, "patch " + std::to_string(p) + ": unsupported boundary condition code " + std::to_string(t));
       DFMI_CHECK(t != WAVE_TRANSMISSIVE || f == "p", "waveTransmissive is supported for p (the 1D flame's outlet)");
-      DFMI_CHECK(t != INLET_OUTLET || f == "U" || f == "p" || f == "Y" || f == "K",
-                 "inletOutlet is supported for U, p, Y and K (energy needs its own mixed form)");
+      DFMI_CHECK(t != INLET_OUTLET || f == "U" || f == "p" || f == "Y" || f == "K" || ras,
+                 "inletOutlet is supported for U, p, Y, K, k and epsilon (energy needs its own mixed form)");
+      DFMI_CHECK(!ras || t == ZERO_GRADIENT || t == FIXED_VALUE || t == INLET_OUTLET || t == CALCULATED || t == EMPTY || t == CYCLIC || bc_proc(t),
+                 "patch " + std::to_string(p) + ": " + f + " takes zeroGradient, fixedValue, inletOutlet, calculated, cyclic, processor, processorCyclic or empty");
       DFMI_CHECK((x.pkind[p] == 1) == (t == CYCLIC) && (x.pkind[p] == 2) == bc_proc(t),
                  "patch " + std::to_string(p) + ": field '" + f + "' type disagrees with the mesh patch kind");
       DFMI_CHECK(t != GRADIENT_ENERGY || f == "he", "gradientEnergy is an energy boundary condition (field 'he')");
@@ -558,6 +607,7 @@ int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* patch_type
       DFMI_CHECK(f != "nut" || t == ZERO_GRADIENT || t == FIXED_VALUE || t == CALCULATED || t == EMPTY || t == CYCLIC || bc_proc(t),
                  "patch " + std::to_string(p) + ": nut takes zeroGradient, fixedValue, calculated, cyclic, processor, processorCyclic or empty");
     }
+    if (ras) ensure_ras_fields(x);
     set_ptype(x, f, patch_type);
     DFMI_HIP(hipStreamSynchronize(x.stream));
   });
@@ -655,7 +705,10 @@ int dfmi_set_scheme(dfmi_ctx* ctx, const char* term, const char* scheme) {
       for (int p : x.pkind) proc |= p == 2;
       DFMI_CHECK(kind == SCH_LINEAR || !proc, t + ": limited schemes on decomposed meshes (processor patches) are not supported");
       x.sch.U = kind; x.sch.k_U = k;
-    } else throw Error("dfmi: unknown scheme term '" + t + "' (div(phi,Yi_h), div(phi,K), div(hDiffCorrFlux), div(phi,U), laplacian)");
+    } else if (t == "div(phi,k)" || t == "div(phi,epsilon)") {
+      DFMI_CHECK(kind == SCH_UPWIND || kind == SCH_LINEAR || kind == SCH_LL, t + ": upwind, limitedLinear or linear");
+      if (t == "div(phi,k)") { x.sch.tk = kind; x.sch.k_tk = k; } else { x.sch.teps = kind; x.sch.k_teps = k; }
+    } else throw Error("dfmi: unknown scheme term '" + t + "' (div(phi,Yi_h), div(phi,K), div(hDiffCorrFlux), div(phi,U), div(phi,k), div(phi,epsilon), laplacian)");
   });
 }
 
@@ -738,6 +791,9 @@ int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long cou
     x.co.fresh = false;
     const std::string n(name ? name : "");
     if (n == "delta" || n == "nut" || n == "boundary_nut") ensure_les_fields(x);
+    if (ras_name(n)) ensure_ras_fields(x);
+    DFMI_CHECK(n != "G" && n != "divU" && n.find("_prebound") == std::string::npos,
+               "field '" + n + "' is formed by dfmi_turbulence_correct and cannot be set");
     DFMI_CHECK(n != "nut", "field 'nut' is formed by dfmi_turbulence_correct and cannot be set (boundary_nut holds the fixed-value slots)");
     DFMI_CHECK(n.rfind("nonorth_", 0) != 0 && n.rfind("boundary_nonorth_", 0) != 0,
                "field '" + n + "' is formed by the library (dfmi_set_scheme \"laplacian\") and cannot be set");
@@ -752,12 +808,16 @@ int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long cou
     if (n == "delta" || n == "U" || n == "boundary_U") x.les.valid = false;
     if (n == "delta") x.les.have_delta = true;
     x.les.zeroed = false;
+    // RAS: nut belongs to k and epsilon and their boundary counterparts
+    static const char* rk[4] = {"k", "epsilon", "boundary_k", "boundary_epsilon"};
+    for (int i = 0; i < 4; ++i) if (n == rk[i]) { x.ras.have[i] = true; x.ras.valid = false; }
   });
 }
 int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, int layout) {
   return guard([&] {
     const std::string n(name ? name : "");
     if (n == "delta" || n == "nut" || n == "boundary_nut") ensure_les_fields(ctx->x);
+    if (ras_name(n)) ensure_ras_fields(ctx->x);
     copy_field(ctx->x, n, host, count, layout, false);
   });
 }
@@ -780,8 +840,9 @@ int dfmi_E_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); le
 int dfmi_turbulence_correct(dfmi_ctx* ctx) {
   return guard([&] {
     DFMI_CHECK(ctx, "null context");
-    if (!ctx->x.les.model) return;   // laminar: nothing to form
+    if (!ctx->x.turbulent()) return;   // laminar: nothing to form
     require_ready(ctx->x);
+    if (ctx->x.ras.model) { ras_correct(ctx->x); return; }   // kEpsilon::correct(): the two equations, then nut
     ensure_les_fields(ctx->x);
     turbulence_correct(ctx->x);
   });
@@ -808,6 +869,7 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
     if (x.steptimer.on && x.steptimer.used == 0) x.steptimer.mark(x.stream);
     x.dnn.prepared = false;         // never reuse a compaction of an earlier (failed) step
     if (x.les.model && !x.les.valid) { ensure_les_fields(x); turbulence_correct(x); }   // turbulence->validate() (dfLowMachFoam.C:207)
+    if (x.ras.model && !x.ras.valid) { ensure_ras_fields(x); ras_nut(x); }                // RAS: correctNut() only, never the equations
     copy_old(x);                    // preTimeStep
     if (x.chem.mode == 2) dnn_prepare(x);   // reacting cells of this step's T (read after the UEqn polls)
     rho_process(x, false);          // rhoEqn (first PIMPLE iteration)
@@ -820,6 +882,8 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
       // rho = psi p: the first corrector's is what correctThermo just wrote (the same product of the same p and psi,
       // halo included); psip0 = psi p feeds only correctPsipRho, skipped below (the field is not updated here)
       if (i > 0) thermo_rho_from_psi(x);
+      const bool ras_tail = x.ras.model && i == n_corr - 1;   // RAS: the last corrector keeps pEqn.H's tail (below)
+      if (ras_tail) thermo_psip0(x);
       if (i > 0 || !early) u_hbya(x);
       // a later corrector may precondition with this step's first hierarchy; with amg.reuse_steps = k > 1 the first
       // corrector too, with the operators of up to k - 1 steps before (rebuilt when they are that old)
@@ -832,7 +896,11 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
       // -- rho = psi p at the next corrector's start, or after the loop (dfLowMachFoam.C:517) -- overwrites before
       // anything reads it (the oracle's time_step runs them: the fields agree bitwise). dfmi_thermo_correct_psip_rho /
       // dfmi_rho_process keep them for callers that read rho in between.
+      // RAS: turbulence->correct() (dfLowMachFoam.C:508) reads that rho -- the last corrector's correctPsipRho and rhoEqn
+      // (the oracle's time_step: rho += psi p - psip0, then the rhoEqn from rho_old and the final phi)
+      if (ras_tail) { thermo_correct_psip_rho(x); rho_process(x, false); }
     }
+    if (x.ras.model) ras_correct(x);   // kEpsilon::correct() on the corrector's rho, before rho = thermo.rho()
     thermo_rho_from_psi(x);         // rho = thermo.rho() (dfLowMachFoam.C:517)
     turbulence_correct(x);          // turbulence->correct() (dfLowMachFoam.C:508) from the last corrector's U; laminar: nothing
     if (x.chem.mode == 1) chem_check(x);   // the p solves' polls have already passed the chemistry
@@ -1044,6 +1112,12 @@ int dfmi_assemble(dfmi_ctx* ctx, const char* eqn) {
       y_prep(x); y_assemble(x);
       bicg_rows_from_ldu_Y(x);
     } else if (e == "E") { conv_weights(x); e_assemble(x); }   // EEqn inspected on its own: fresh div(phi,Yi_h) weights
+    else if (e == "k" || e == "epsilon") {   // from the fields as they stand, no solve in between
+      DFMI_CHECK(x.ras.model, "dfmi_assemble: '" + e + "' needs ras.model != 0");
+      ensure_ras_fields(x);
+      ras_production(x);
+      ras_assemble(x, e == "k" ? 1 : 0);
+    }
     else if (e == "p") {
       p_assemble(x);
       // corrected laplacian: the source of the corrector loop's first pass (do_p_nonorth)
@@ -1061,7 +1135,8 @@ int dfmi_get_matrix(dfmi_ctx* ctx, const char* eqn, const char* part, double* ho
   return guard([&] {
     Ctx& x = ctx->x;
     std::string e(eqn), p(part);
-    Matrix* A = e == "U" ? &x.mU : e == "Y" ? &x.mY : e == "E" ? &x.mE : e == "p" ? &x.mP : nullptr;
+    Matrix* A = e == "U" ? &x.mU : e == "Y" ? &x.mY : e == "E" ? &x.mE : e == "p" ? &x.mP
+                : (e == "k" || e == "epsilon") ? &x.mK : nullptr;   // k / epsilon: the scalar assembly's, whichever it formed last
     DFMI_CHECK(A, "unknown equation '" + e + "'");
     DevBuf<double>* b = p == "lower" ? &A->lower : p == "upper" ? &A->upper : p == "diag" ? &A->diag :
                         p == "source" ? &A->source : p == "source_solve" ? &A->source_solve :
@@ -1095,7 +1170,7 @@ int dfmi_get_solver_rows(dfmi_ctx* ctx, const char* eqn, const char* part, doubl
 int dfmi_set_solver(dfmi_ctx* ctx, const char* eqn, int max_iter, double tol, double abs_tol) {
   return guard([&] {
     std::string e(eqn);
-    DFMI_CHECK(e == "U" || e == "Y" || e == "E" || e == "p", "unknown equation '" + e + "'");
+    DFMI_CHECK(e == "U" || e == "Y" || e == "E" || e == "p" || e == "k" || e == "epsilon", "unknown equation '" + e + "'");
     DFMI_CHECK(max_iter > 0 && tol >= 0 && abs_tol >= 0, "bad solver controls");
     SolverCfg& c = ctx->x.solver[e];
     c.max_iter = max_iter; c.tol = tol; c.abs_tol = abs_tol;
@@ -1320,9 +1395,25 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
         DFMI_CHECK(value > 0 && value <= 1.79769313486231570e308, "dfmi_set_option: " + k + " must be positive and finite");
       // nut belongs to the model and its coefficients (Prt and Sct enter the effective fields, formed at every
       // assembly, but a changed coefficient invalidates all the same: one rule)
+      DFMI_CHECK(k != "les.model" || value == 0.0 || !x.ras.model,
+                 "dfmi_set_option: les.model != 0 and ras.model != 0 exclude each other (one turbulence model at a time)");
       if (value != x.opt(key)) { x.les.valid = false; x.les.zeroed = false; }
       if (k == "les.model") x.les.model = (int)value;
       if (x.les.model && x.have_bgeom) ensure_les_fields(x);
+    }
+    if (k.rfind("ras.", 0) == 0) {
+      if (k == "ras.model") {
+        DFMI_CHECK(value == 0.0 || value == 1.0, "dfmi_set_option: ras.model must be 0 (none) or 1 (kEpsilon)");
+        DFMI_CHECK(value == 0.0 || !x.les.model,
+                   "dfmi_set_option: ras.model != 0 and les.model != 0 exclude each other (one turbulence model at a time)");
+      } else if (k == "ras.C3")
+        DFMI_CHECK(value >= -1.79769313486231570e308 && value <= 1.79769313486231570e308, "dfmi_set_option: ras.C3 must be finite");
+      else
+        DFMI_CHECK(value > 0 && value <= 1.79769313486231570e308, "dfmi_set_option: " + k + " must be positive and finite");
+      // nut belongs to the model and its coefficients: one rule, as for les.*
+      if (value != x.opt(key)) { x.ras.valid = false; x.les.valid = false; x.les.zeroed = false; }
+      if (k == "ras.model") x.ras.model = (int)value;
+      if (x.ras.model && x.have_bgeom) ensure_ras_fields(x);
     }
     x.opts[k] = value;
   });
@@ -1335,7 +1426,7 @@ int dfmi_get_option(dfmi_ctx* ctx, const char* key, double* value) {
 int dfmi_set_preconditioner(dfmi_ctx* ctx, const char* eqn, const char* name) {
   return guard([&] {
     std::string e(eqn), n(name);
-    DFMI_CHECK(e == "U" || e == "Y" || e == "E" || e == "p", "unknown equation '" + e + "'");
+    DFMI_CHECK(e == "U" || e == "Y" || e == "E" || e == "p" || e == "k" || e == "epsilon", "unknown equation '" + e + "'");
     DFMI_CHECK(n == "jacobi" || (n == "amg" && e == "p"), "preconditioner must be 'jacobi' or ('amg' for p)");
     ctx->x.solver[e].precond = n == "amg" ? 1 : 0;
   });

@@ -58,6 +58,8 @@ enum SchemeKind { SCH_UPWIND = 0, SCH_LINEAR = 1, SCH_LL = 2, SCH_LL01 = 3, SCH_
 struct Schemes {
   int yh = SCH_UPWIND, K = SCH_LINEAR, hD = SCH_LINEAR, U = SCH_LINEAR;
   double k_yh = 1.0, k_K = 1.0, k_U = 1.0;
+  int tk = SCH_UPWIND, teps = SCH_UPWIND;   // div(phi,k), div(phi,epsilon) (RAS)
+  double k_tk = 1.0, k_teps = 1.0;
 };
 
 struct Field {
@@ -277,6 +279,17 @@ inline const OptDef* option_defs(int& n) {
     {"les.Cw", 0.325},                // WALE
     {"les.Prt", 1.0},                 // alphaEff = alpha + mut / Prt (createFields.H:133)
     {"les.Sct", 1.0},                 // DEff_i = rhoD_i + mut / Sct
+    {"ras.model", 0},                 // turbulence->: 0 none, 1 kEpsilon (RAS; include/dfmi.h)
+    {"ras.Cmu", 0.09},                // nut = Cmu k^2 / epsilon
+    {"ras.C1", 1.44},                 // epsilon production
+    {"ras.C2", 1.92},                 // epsilon destruction
+    {"ras.C3", 0.0},                  // epsilon dilatation term ((2/3) C1 - C3) rho divU; any finite value
+    {"ras.sigmak", 1.0},              // Dk = rho (nut / sigmak + mu / rho)
+    {"ras.sigmaEps", 1.3},            // Deps = rho (nut / sigmaEps + mu / rho)
+    {"ras.kMin", 1e-15},              // bound(k, kMin)
+    {"ras.epsilonMin", 1e-15},        // bound(epsilon, epsilonMin)
+    {"ras.Prt", 1.0},                 // alphaEff = alpha + mut / Prt (RAS mode)
+    {"ras.Sct", 1.0},                 // DEff_i = rhoD_i + mut / Sct (RAS mode)
     {"p.n_nonorth", 0},               // nNonOrthogonalCorrectors (system/fvSolution PIMPLE): extra passes of the pEqn's
                                       // non-orthogonal corrector loop (pEqn.H:51-62)
   };
@@ -355,6 +368,7 @@ struct Ctx {
   std::map<std::string, Field> fields;
   // matrices
   Matrix mU, mY, mE, mP;
+  Matrix mK;                     // the generic scalar transport assembly's (k_scalar_assemble: epsilon, then k); RAS mode only
   std::map<std::string, SolverCfg> solver;
   Thermo thermo;
   // scratch
@@ -425,6 +439,7 @@ struct Ctx {
   std::map<std::string, StatSnap> stat_snap;
   std::map<std::string, int> solve_expect;   // iterations of the last solve per equation (linsolve.hip Poller)
   DevBuf<double> work;           // per equation (U, Y, E, p): system-iterations, summed on the device
+  DevBuf<double> work_ras;       // the same for epsilon and k (allocated by their first solve)
   KernelTimer ktimer;
   StepTimer steptimer;
   CommStats comm;
@@ -436,11 +451,17 @@ struct Ctx {
   // read at every launch), whether the field "nut" belongs to the model, delta and U as they stand, and whether the
   // fields the dropped terms read (sumYDiffError, hDiffCorrFlux, diffAlphaD, phiUc) have been zeroed for this mode
   struct Les { int model = 0; bool valid = false, zeroed = false, have_delta = false; } les;
-  // what the three assemblies read as mu / alpha: the thermo's fields, or in LES mode muEff / alphaEff (les_effective)
-  double* visc(bool boundary) { return f(std::string(boundary ? "boundary_" : "") + (les.model ? "muEff" : "mu")); }
-  double* cond(bool boundary) { return f(std::string(boundary ? "boundary_" : "") + (les.model ? "alphaEff" : "alpha")); }
+  // RAS k-epsilon (options ras.*, fv_kernels.hip ras_*): the model in force, whether nut belongs to k and epsilon as
+  // they stand, and which of k, epsilon, boundary_k, boundary_epsilon the caller has set
+  struct Ras { int model = 0; bool valid = false; bool have[4] = {false, false, false, false}; } ras;
+  // the one flag everything downstream of an eddy viscosity reads: either model sets it (the effective fields, the
+  // dropped YEqn / EEqn terms, the LES instantiations of the assemblies)
+  bool turbulent() const { return les.model != 0 || ras.model != 0; }
+  // what the three assemblies read as mu / alpha: the thermo's fields, or in turbulent mode muEff / alphaEff (les_effective)
+  double* visc(bool boundary) { return f(std::string(boundary ? "boundary_" : "") + (turbulent() ? "muEff" : "mu")); }
+  double* cond(bool boundary) { return f(std::string(boundary ? "boundary_" : "") + (turbulent() ? "alphaEff" : "alpha")); }
   // mut / Sct, which the species kernels add where they read rhoD (nullptr: laminar)
-  double* mut_sct(bool boundary) { return les.model ? f(boundary ? "boundary_mutSct" : "mutSct") : nullptr; }
+  double* mut_sct(bool boundary) { return turbulent() ? f(boundary ? "boundary_mutSct" : "mutSct") : nullptr; }
 
   MeshView view() const {
     MeshView m;
@@ -473,7 +494,7 @@ struct Ctx {
   const double* sch_w(int i) {
     static const char* names[8] = {"conv_w", "boundary_conv_w", "K_w", "boundary_K_w", "cubic_flux",
                                    "boundary_cubic_flux", "U_w", "boundary_U_w"};
-    const bool on = i < 2 ? sch.yh != SCH_UPWIND : i < 4 ? sch.K != SCH_LINEAR : i < 6 ? sch.hD == SCH_CUBIC && !les.model
+    const bool on = i < 2 ? sch.yh != SCH_UPWIND : i < 4 ? sch.K != SCH_LINEAR : i < 6 ? sch.hD == SCH_CUBIC && !turbulent()
                                                                                      : sch.U == SCH_LLV;
     if (!on) return nullptr;
     auto it = fields.find(names[i]);
@@ -552,6 +573,14 @@ void turbulence_correct(Ctx& x);
 // slot from the slot's own values, from the fields as they stand (after the rhoEqn, before the three assemblies);
 // the first call in LES mode also zeroes the fields of the dropped terms. Throws when nut is not valid.
 void les_effective(Ctx& x);
+// RAS k-epsilon (options ras.*; include/dfmi.h). ras_production: G and divU from U, phi, rho and the old nut.
+// ras_assemble: one equation's sources, diffusivity and matrix (keq 0: epsilon, 1: k) into Ctx::mK from the fields as they
+// stand. ras_post_solve: the solved field's boundary values, bound() and the halo. ras_nut: correctNut() -- nut = Cmu k^2 /
+// epsilon on cells and slots, then Ctx::ras.valid. The solves between them are the caller's (capi.cpp ras_correct).
+void ras_production(Ctx& x);
+void ras_assemble(Ctx& x, int keq);
+void ras_post_solve(Ctx& x, int keq);
+void ras_nut(Ctx& x);
 // laplacian schemes. nonorth_setup: the non-orthogonal delta coefficients and correction vectors from Sf,
 // mesh_distance and the patch deltas (surfaceInterpolation::makeNonOrthDeltaCoeffs / makeNonOrthCorrectionVectors).
 // nonorth_p_correct: the pEqn's explicit term from the current p / boundary_p -- source = base + div of the face flux

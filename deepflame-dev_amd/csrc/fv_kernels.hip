@@ -2160,6 +2160,159 @@ __global__ void __launch_bounds__(TPB) k_e_assemble(MeshView m, const int8_t* __
   });
 }
 
+// ------------------------------------------------------------------ RAS k-epsilon (include/dfmi.h)
+// OpenFOAM-7 kEpsilon::correct() / correctNut() / bound() as the header states them. Every kernel is a per-cell
+// gather or a pointwise pass: one accumulator per term, faces in the sequential order, no atomics, no pow().
+struct RasCoef { double Cmu, C1, C2, C3, sigmak, sigmaEps, kMin, epsMin; };
+
+// dd = dev(twoSymm(g)) && g with T = g + g^T, t3 = (1/3) tr T:
+//   ((T00 - t3) g00 + (T11 - t3) g11 + (T22 - t3) g22) + ((T01 g01 + T01 g10) + (T02 g02 + T02 g20) + (T12 g12 + T12 g21))
+__device__ __forceinline__ double ras_dev_two_symm_dd(const double (&g)[9]) {
+  const double T00 = g[0] + g[0], T11 = g[4] + g[4], T22 = g[8] + g[8];
+  const double T01 = g[1] + g[3], T02 = g[2] + g[6], T12 = g[5] + g[7];
+  const double t3 = (1.0 / 3.0) * ((T00 + T11) + T22);
+  const double dg = ((T00 - t3) * g[0] + (T11 - t3) * g[4]) + (T22 - t3) * g[8];
+  const double off = ((T01 * g[1] + T01 * g[3]) + (T02 * g[2] + T02 * g[6])) + (T12 * g[5] + T12 * g[7]);
+  return dg + off;
+}
+// G = nut (dev(twoSymm(g)) && g) and divU = fvc::div(phi / interpolate(rho)) per cell: grad_u_cell's gather (bitwise the
+// UEqn's gradient), then a second walk over the same faces for the volumetric flux (phi, rho of the face neighbours;
+// the slots' face density by rho's patch types: the stored value, or the interpolate on a coupled slot). Both are
+// written out, 16 B per cell: the epsilon and the k assembly read them with a solve in between.
+template <int WT>
+__global__ void __launch_bounds__(TPB) k_ras_production(MeshView m, const int8_t* __restrict__ tyU, const int8_t* __restrict__ tyR,
+    const double* __restrict__ U, const double* __restrict__ bU, const double* __restrict__ phi,
+    const double* __restrict__ bphi, const double* __restrict__ rho, const double* __restrict__ brho,
+    const double* __restrict__ nut, double* __restrict__ G, double* __restrict__ divU) {
+  const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
+  if (c >= m.C) return;
+  double g[9];
+  grad_u_cell<WT>(m, tyU, U, bU, c, g);
+  const double rc = rho[c];
+  double dv = 0.0;
+  each_face<WT>(m, c, [&](int f, int o2, bool own) {
+    const double w = m.w[f], rn = rho[o2];
+    const double v = phi[f] / (own ? interp_f(w, rc, rn) : interp_f(w, rn, rc));
+    if (own) dv += v; else dv -= v;
+  });
+  each_slot(m, tyR, c, [&](int b, int t) { dv += bphi[b] / bface(m, t, rho, brho, b, c); });
+  divU[c] = dv / m.V[c];
+  G[c] = nut[c] * ras_dev_two_symm_dd(g);
+}
+
+// D = rho (nut / sigma + mu / rho) over n cells or n boundary slots (each slot from its own boundary values)
+__device__ __forceinline__ double ras_diff(double rho, double nut, double mu, double sigma) {
+  return rho * (nut / sigma + mu / rho);
+}
+__global__ void k_ras_diffusivity(long n, const double* __restrict__ rho, const double* __restrict__ nut,
+                                  const double* __restrict__ mu, double sigma, double* __restrict__ D) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  D[i] = ras_diff(rho[i], nut[i], mu[i], sigma);
+}
+// explicit source Su and implicit coefficient Sp (per unit volume) of one of the two equations, and its cell diffusivity:
+//   epsilon (keq = 0): a = (((2/3) C1 - C3) rho) divU;  Su = ((C1 rho) G) (eps / k) - min(a, 0) eps;  Sp = max(a, 0) + (C2 rho) (eps / k)
+//   k       (keq = 1): a = ((2/3) rho) divU;            Su = rho G - min(a, 0) k;                     Sp = max(a, 0) + rho (eps / k)
+__global__ void k_ras_sources(long n, int keq, RasCoef q, const double* __restrict__ G, const double* __restrict__ divU,
+                              const double* __restrict__ rho, const double* __restrict__ k, const double* __restrict__ eps,
+                              const double* __restrict__ nut, const double* __restrict__ mu, double* __restrict__ Su,
+                              double* __restrict__ Sp, double* __restrict__ D) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double r = rho[i], kc = k[i], ec = eps[i], ek = ec / kc;
+  if (keq) {
+    const double a = ((2.0 / 3.0) * r) * divU[i];
+    Su[i] = r * G[i] - fmin(a, 0.0) * kc;
+    Sp[i] = fmax(a, 0.0) + r * ek;
+    D[i] = ras_diff(r, nut[i], mu[i], q.sigmak);
+  } else {
+    const double a = (((2.0 / 3.0) * q.C1 - q.C3) * r) * divU[i];
+    Su[i] = ((q.C1 * r) * G[i]) * ek - fmin(a, 0.0) * ec;
+    Sp[i] = fmax(a, 0.0) + (q.C2 * r) * ek;
+    D[i] = ras_diff(r, nut[i], mu[i], q.sigmaEps);
+  }
+}
+
+// Generic scalar transport assembly: ddt(rho, psi) + div(phi, psi) - laplacian(D, psi) == Su - Sp psi (Su, Sp per
+// unit volume), Euler ddt with rho_old and the field's own value, convection by the weights wc / bwc (nullptr:
+// upwind), the laplacian by the delta coefficients of the scheme in force. The face and slot arithmetic is
+// k_e_assemble's he part; the boundary coefficients k_y_assemble's (inletOutlet included):
+//   diag = ((rdt rho V + d1) - dL) + V Sp;   source = rdt rho_old psi V + V Su
+template <int WT>
+__global__ void __launch_bounds__(TPB) k_scalar_assemble(MeshView m, const int8_t* __restrict__ ty,
+    const double* __restrict__ psi, const double* __restrict__ bpsi, const double* __restrict__ rho,
+    const double* __restrict__ rho_old, const double* __restrict__ phi, const double* __restrict__ bphi,
+    const double* __restrict__ D, const double* __restrict__ bD, const double* __restrict__ Su,
+    const double* __restrict__ Sp, double* __restrict__ lower, double* __restrict__ upper, double* __restrict__ diag,
+    double* __restrict__ src, double* __restrict__ ic, double* __restrict__ bc, MixBC mx,
+    const double* __restrict__ wc, const double* __restrict__ bwc) {
+  const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
+  if (c >= m.C) return;
+  const long B = m.B;
+  double d1 = 0.0, dL = 0.0;
+  const double Dc = D[c];
+  each_face<WT>(m, c, [&](int f, int o2, bool own) {
+    const double ph = phi[f], w = m.w[f];
+    const double wu = wc ? wc[f] : (ph >= 0 ? 1.0 : 0.0);
+    const double L1 = -wu * ph, U1 = L1 + ph;
+    const double UL = m.dc[f] * ((own ? interp_f(w, Dc, D[o2]) : interp_f(w, D[o2], Dc)) * m.magSf[f]);
+    if (own) { d1 -= L1; lower[f] = L1 - UL; upper[f] = U1 - UL; } else d1 -= U1;
+    dL -= UL;
+  });
+  const double vol = m.V[c];
+  diag[c] = ((m.rdt * rho[c] * vol + d1) - dL) + vol * Sp[c];
+  src[c] = m.rdt * rho_old[c] * psi[c] * vol + vol * Su[c];
+  each_slot(m, ty, c, [&](int b, int t) {
+    const double wu = bwc ? bwc[b] : upwind_b(m, bphi, b);
+    const BCoef qc = bcoef_f(t, bpsi[b], wu, m.bdc[b], mx, b, B, 0);
+    const BCoef ql = bcoef_f(t, bpsi[b], m.bw[b], m.bdc[b], mx, b, B, 0);
+    const double gam = bc_coupled(t) ? interp_b(m.bw[b], Dc, nbrv(m, D, bD, b)) : bD[b];
+    const double pG = gam * m.bmagSf[b];
+    ic[b] = bphi[b] * qc.vic - pG * ql.gic;
+    bc[b] = -bphi[b] * qc.vbc - (-pG * ql.gbc);
+  });
+}
+
+// bound(psi, lo) (OpenFOAM-7 bound.C) as a gather from the solved field `pre` (its slots bpre corrected after the solve):
+//   avg = sum_f |Sf| face(max(pre, lo)) / sum_f |Sf| over the cell's faces (interp_f of the two bounded cell values,
+//   owner first) and its slots (a coupled slot is a face: interp_b of the two bounded cell values, so the result does
+//   not depend on where a decomposition cuts; every other slot max(stored value, lo));
+//   psi = max(max(pre, avg pos0(-pre)), lo). A cell with pre >= lo comes out bitwise pre.
+template <int WT>
+__global__ void __launch_bounds__(TPB) k_ras_bound(MeshView m, const int8_t* __restrict__ ty, const double* __restrict__ pre,
+                                                   const double* __restrict__ bpre, double lo, double* __restrict__ psi) {
+  const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
+  if (c >= m.C) return;
+  const double pc = pre[c], pcb = fmax(pc, lo);
+  double num = 0.0, den = 0.0;
+  each_face<WT>(m, c, [&](int f, int o2, bool own) {
+    const double w = m.w[f], ms = m.magSf[f], pn = fmax(pre[o2], lo);
+    num += ms * (own ? interp_f(w, pcb, pn) : interp_f(w, pn, pcb));
+    den += ms;
+  });
+  each_slot(m, ty, c, [&](int b, int t) {
+    const double ms = m.bmagSf[b];
+    num += ms * (bc_coupled(t) ? interp_b(m.bw[b], pcb, fmax(nbrv(m, pre, bpre, b), lo)) : fmax(bpre[b], lo));
+    den += ms;
+  });
+  psi[c] = fmax(fmax(pc, (num / den) * pos0(-pc)), lo);
+}
+__global__ void k_ras_bound_slots(long n, double lo, double* __restrict__ bpsi) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  bpsi[i] = fmax(bpsi[i], lo);
+}
+// nut = (Cmu (k k)) / eps over n cells, or over the n boundary slots whose nut patch type is `calculated` (the field
+// expression's own boundary values; the other types are nut.correctBoundaryConditions(), k_bc_correct)
+__global__ void k_ras_nut(long n, const int8_t* __restrict__ ty, double Cmu, const double* __restrict__ k,
+                          const double* __restrict__ eps, double* __restrict__ nut) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (ty && ty[i] != CALCULATED) return;
+  const double kc = k[i];
+  nut[i] = (Cmu * (kc * kc)) / eps[i];
+}
+
 // ------------------------------------------------------------------ non-orthogonal laplacians
 // surfaceInterpolation::makeNonOrthDeltaCoeffs / makeNonOrthCorrectionVectors per face of the face storage, from the
 // arrays the context holds (Sf, |Sf|, d = mesh_distance), in Mesh.nonorth_geometry's operation order:
@@ -2428,14 +2581,14 @@ bool face_hex(const Ctx& x) { return x.hex[0] > 0 && x.on("fv.hex_walk") && !x.o
 // the YEqn assembly kernels, whose LES form (Ctx::les.model != 0) is an instantiation of its own
 // (the kernels' last argument, LesDiff<L>, is appended here)
 #define LAUNCH_SWGL(kern, NS, n, ...) \
-  do { if (x.les.model) LAUNCH((kern<NS, 0, true>), n, __VA_ARGS__, les_diff<true>(x)); \
+  do { if (x.turbulent()) LAUNCH((kern<NS, 0, true>), n, __VA_ARGS__, les_diff<true>(x)); \
        else LAUNCH((kern<NS, 0, false>), n, __VA_ARGS__, les_diff<false>(x)); } while (0)
 #define LAUNCH_SW_(kern, NS, L, n, ...) \
   do { if (face_hex(x)) LAUNCH((kern<NS, -1, L>), n, __VA_ARGS__, les_diff<L>(x)); \
        else if (face_rows(x)) LAUNCH((kern<NS, 6, L>), n, __VA_ARGS__, les_diff<L>(x)); \
        else LAUNCH((kern<NS, 0, L>), n, __VA_ARGS__, les_diff<L>(x)); } while (0)
 #define LAUNCH_SWL(kern, NS, n, ...) \
-  do { if (x.les.model) LAUNCH_SW_(kern, NS, true, n, __VA_ARGS__); else LAUNCH_SW_(kern, NS, false, n, __VA_ARGS__); } while (0)
+  do { if (x.turbulent()) LAUNCH_SW_(kern, NS, true, n, __VA_ARGS__); else LAUNCH_SW_(kern, NS, false, n, __VA_ARGS__); } while (0)
 #define LAUNCH_SW(kern, NS, n, ...) \
   do { if (face_hex(x)) LAUNCH((kern<NS, -1>), n, __VA_ARGS__); else if (face_rows(x)) LAUNCH((kern<NS, 6>), n, __VA_ARGS__); \
        else LAUNCH((kern<NS, 0>), n, __VA_ARGS__); } while (0)
@@ -2589,8 +2742,9 @@ void turbulence_correct(Ctx& x) {
 }
 
 void les_effective(Ctx& x) {
-  if (!x.les.model) return;
-  DFMI_CHECK(x.les.valid, "LES: nut is not valid (the model, a coefficient, delta or U changed): call dfmi_turbulence_correct");
+  if (!x.turbulent()) return;
+  if (x.ras.model) { if (!x.ras.valid) ras_nut(x); }   // turbulence->validate(): correctNut() from k and epsilon as they stand
+  else DFMI_CHECK(x.les.valid, "LES: nut is not valid (the model, a coefficient, delta or U changed): call dfmi_turbulence_correct");
   double* cell[3] = {scheme_buf(x, "muEff", x.C, 1), scheme_buf(x, "alphaEff", x.C, 1), scheme_buf(x, "mutSct", x.C, 1)};
   double* slot[3] = {scheme_buf(x, "boundary_muEff", x.B, 1), scheme_buf(x, "boundary_alphaEff", x.B, 1),
                      scheme_buf(x, "boundary_mutSct", x.B, 1)};
@@ -2599,7 +2753,7 @@ void les_effective(Ctx& x) {
       for (const char* pre : {"", "boundary_"}) x.fields.at(std::string(pre) + n).buf.zero(x.stream);
     x.les.zeroed = true;
   }
-  const double Prt = x.opt("les.Prt"), Sct = x.opt("les.Sct");
+  const double Prt = x.opt(x.ras.model ? "ras.Prt" : "les.Prt"), Sct = x.opt(x.ras.model ? "ras.Sct" : "les.Sct");
   LAUNCH(k_les_effective, x.C, (long)x.C, x.f("rho"), x.f("nut"), x.f("mu"), x.f("alpha"), Prt, Sct, cell[0], cell[1], cell[2]);
   LAUNCH(k_les_effective, x.B, (long)x.B, x.f("boundary_rho"), x.f("boundary_nut"), x.f("boundary_mu"),
          x.f("boundary_alpha"), Prt, Sct, slot[0], slot[1], slot[2]);
@@ -2750,7 +2904,7 @@ static void e_scheme_terms(Ctx& x) {
       LAUNCH(k_upwind_w_slot, x.B, m, x.f("boundary_phi"), bw);
     }
   }
-  if (x.sch.hD == SCH_CUBIC && !x.les.model) {   // LES: no div(hDiffCorrFlux) (EEqn.H:30-36), so no correction of it
+  if (x.sch.hD == SCH_CUBIC && !x.turbulent()) {   // LES: no div(hDiffCorrFlux) (EEqn.H:30-36), so no correction of it
     double* cf = scheme_buf(x, "cubic_flux", x.Fs, 1, true);
     double* bcf = scheme_buf(x, "boundary_cubic_flux", x.B, 1);
     double* g = scheme_buf(x, "gradHD", x.C, 9);
@@ -2770,7 +2924,7 @@ void y_prep(Ctx& x, bool weights) {
   if (weights) conv_weights(x);   // div(phi,Yi_h) weights of this step (before Y changes)
   // LES (simulationType != laminar): the reference drops fvmDiv(phiUc, Yi), diffAlphaD and div(hDiffCorrFlux)
   // (YEqn.H:101-106, EEqn.H:30-36) -- everything below; their fields stay zero (les_effective)
-  if (x.les.model) return;
+  if (x.turbulent()) return;
   MeshView m = x.view();
   double* gout = x.fields.count("dbg_gradY") ? x.f("dbg_gradY") : nullptr;
 // (k_y_prep: the CSR walk measured faster than the gather rows -- 667 vs 848 us on the 2M box; its
@@ -2948,7 +3102,7 @@ static void nonorth_y(Ctx& x, double* src, double* rhs, long Ce) {
   a.g = g; a.bg = x.f("boundary_nonorth_gradY");
   a.gam = x.f("rhoD"); a.bgam = x.f("boundary_rhoD"); a.add = x.mut_sct(false); a.badd = x.mut_sct(true);
   a.src = src; a.rhs = rhs; a.Ce = Ce; a.S = x.S; a.inert = x.inert;
-  if (!x.les.model) {   // LES drops diffAlphaD (y_prep)
+  if (!x.turbulent()) {   // LES / RAS drop diffAlphaD (y_prep)
     a.alpha = x.f("alpha"); a.balpha = x.f("boundary_alpha"); a.hai = x.f("hai"); a.bhai = x.f("boundary_hai");
     a.dAD = x.f("diffAlphaD");
   }
@@ -2991,6 +3145,103 @@ void nonorth_p_flux(Ctx& x) {
   const MeshView m = x.view();
   LAUNCH(k_nonorth_flux_face, x.Fs, m, x.f("nonorth_p_flux"), x.f("phi"));
   LAUNCH(k_nonorth_flux_slot, x.B, m, x.st("p"), x.f("boundary_nonorth_p_flux"), x.f("boundary_phi"));
+}
+
+// ---- RAS k-epsilon (include/dfmi.h)
+static RasCoef ras_coef(Ctx& x) {
+  return {x.opt("ras.Cmu"), x.opt("ras.C1"), x.opt("ras.C2"), x.opt("ras.C3"), x.opt("ras.sigmak"), x.opt("ras.sigmaEps"),
+          x.opt("ras.kMin"), x.opt("ras.epsilonMin")};
+}
+static void ras_check_set(Ctx& x) {
+  static const char* names[4] = {"k", "epsilon", "boundary_k", "boundary_epsilon"};
+  for (int i = 0; i < 4; ++i)
+    DFMI_CHECK(x.ras.have[i], std::string("RAS: the field '") + names[i] + "' is not set (dfmi_set_field)");
+}
+void ras_production(Ctx& x) {
+  ras_check_set(x);
+  // several ranks: the neighbour half of the processor slots of k and epsilon as the caller set them (the limiter's and
+  // the corrected laplacian's gradients read the cell across a processor face; later calls find what ras_post_solve left)
+  halo_fields(x, {"k", "epsilon"});
+  if (!x.ras.valid) ras_nut(x);   // the old nut of k and epsilon as they stand
+  LAUNCH_W(k_ras_production, x.C, x.view(), x.st("U"), x.st("rho"), x.f("U"), x.f("boundary_U"), x.f("phi"),
+           x.f("boundary_phi"), x.f("rho"), x.f("boundary_rho"), x.f("nut"), x.f("G"), x.f("divU"));
+}
+// convection weights of one scalar (dfmi_set_scheme div(phi,k) / div(phi,epsilon)): nullptr for upwind, the mesh's for
+// linear, k_lim_w_* from the gradient g / bg for limitedLinear
+static void ras_weights(Ctx& x, int kind, double kcoef, const char* nm, const double* g, const double* bg, const double*& w,
+                        const double*& bw) {
+  w = nullptr; bw = nullptr;
+  if (kind == SCH_UPWIND) return;
+  if (kind == SCH_LINEAR) { w = x.w.p; bw = x.bw.p; return; }
+  const MeshView m = x.view();
+  const std::string bn = std::string("boundary_") + nm;
+  double* wo = scheme_buf(x, "ras_w", x.Fs, 1, true);
+  double* bwo = scheme_buf(x, "boundary_ras_w", x.B, 1);
+  const double twoByk = 2.0 / std::max(kcoef, 1e-15);
+  if (face_hex(x)) LAUNCH(k_lim_w_cell, x.C, m, 0, twoByk, x.f("phi"), x.f(nm), g, wo);
+  else LAUNCH(k_lim_w_face, x.Fs, m, 0, twoByk, x.f("phi"), x.f(nm), g, wo);
+  LAUNCH(k_lim_w_slot, x.B, m, x.st(nm), 0, twoByk, x.f("boundary_phi"), x.f(nm), x.f(bn), g, bg, bwo);
+  w = wo; bw = bwo;
+}
+void ras_assemble(Ctx& x, int keq) {
+  ras_check_set(x);
+  const char* nm = keq ? "k" : "epsilon";
+  const std::string bn = std::string("boundary_") + nm;
+  const RasCoef q = ras_coef(x);
+  const MeshView m = x.view();
+  Matrix& A = x.mK;
+  LAUNCH(k_ras_sources, x.C, (long)x.C, keq, q, x.f("G"), x.f("divU"), x.f("rho"), x.f("k"), x.f("epsilon"), x.f("nut"),
+         x.f("mu"), x.f("ras_Su"), x.f("ras_Sp"), x.f("ras_D"));
+  LAUNCH(k_ras_diffusivity, x.B, (long)x.B, x.f("boundary_rho"), x.f("boundary_nut"), x.f("boundary_mu"),
+         keq ? q.sigmak : q.sigmaEps, x.f("boundary_ras_D"));
+  const int kind = keq ? x.sch.tk : x.sch.teps;
+  const bool lim = kind == SCH_LL, corr = x.lap == LAP_CORRECTED;
+  const int8_t* ty = x.st(nm);
+  double *g = nullptr, *bg = nullptr;
+  if (lim || corr) {   // the field's Gauss gradient: the limiter's upwind-cell gradient and the corrected laplacian's
+    if (lim) scheme_checks(x, true);
+    g = scheme_buf(x, "ras_grad", x.C, 3);
+    bg = scheme_buf(x, "boundary_ras_grad", x.B, 3);
+    LAUNCH_GRAD(1, ty, x.f(nm), x.f(bn), g);
+    halo_fields(x, {"ras_grad"});   // the neighbour cell's gradient on processor faces
+  }
+  const double *w, *bw;
+  ras_weights(x, kind, keq ? x.sch.k_tk : x.sch.k_teps, nm, g, bg, w, bw);
+  LAUNCH_W(k_scalar_assemble, x.C, m, ty, x.f(nm), x.f(bn), x.f("rho"), x.f("rho_old"), x.f("phi"), x.f("boundary_phi"),
+           x.f("ras_D"), x.f("boundary_ras_D"), x.f("ras_Su"), x.f("ras_Sp"), A.lower.p, A.upper.p, A.diag.p, A.source.p,
+           A.ic.p, A.bc.p, mixbc(x, nm), w, bw);
+  if (corr) {   // - fvm::laplacian(D, psi): the explicit non-orthogonal term
+    NoArgs a = no_args(x);
+    a.g = g; a.bg = bg;
+    a.gam = x.f("ras_D"); a.bgam = x.f("boundary_ras_D");
+    a.src = A.source.p;
+    LAUNCH_NO(1, NO_SHARED, ty, a);
+  }
+}
+// after the solve: the field's boundary values and halo (fvMatrix::solve's correctBoundaryConditions), then bound()
+// as a gather from a copy of the solved field, max(., lo) on every slot, and the bounded cells' halo
+void ras_post_solve(Ctx& x, int keq) {
+  const char* nm = keq ? "k" : "epsilon";
+  const std::string bn = std::string("boundary_") + nm, pre = std::string(nm) + "_prebound", bpre = "boundary_" + pre;
+  const double lo = x.opt(keq ? "ras.kMin" : "ras.epsilonMin");
+  k_bc_correct(x, nm, x.f(nm), x.f(bn), 1);
+  halo_fields(x, {nm});
+  DFMI_HIP(hipMemcpyAsync(x.f(pre), x.f(nm), sizeof(double) * x.C, hipMemcpyDeviceToDevice, x.stream));
+  if (x.B) DFMI_HIP(hipMemcpyAsync(x.f(bpre), x.f(bn), sizeof(double) * x.B, hipMemcpyDeviceToDevice, x.stream));
+  LAUNCH_W(k_ras_bound, x.C, x.view(), x.st(nm), x.f(pre), x.f(bpre), lo, x.f(nm));
+  LAUNCH(k_ras_bound_slots, x.B, (long)x.B, lo, x.f(bn));
+  halo_fields(x, {nm});
+}
+// correctNut(): nut = Cmu k^2 / epsilon on cells and on nut's `calculated` slots, boundary_nut by nut's patch types, halo
+void ras_nut(Ctx& x) {
+  ras_check_set(x);
+  const double Cmu = x.opt("ras.Cmu");
+  const char* tn = x.stype.count("nut") ? "nut" : "calculated";
+  LAUNCH(k_ras_nut, x.C, (long)x.C, (const int8_t*)nullptr, Cmu, x.f("k"), x.f("epsilon"), x.f("nut"));
+  LAUNCH(k_ras_nut, x.B, (long)x.B, x.st(tn), Cmu, x.f("boundary_k"), x.f("boundary_epsilon"), x.f("boundary_nut"));
+  k_bc_correct(x, tn, x.f("nut"), x.f("boundary_nut"), 1);
+  halo_fields(x, {"nut"});
+  x.ras.valid = true;
 }
 #undef LAUNCH_GRAD
 #undef LAUNCH_NO

@@ -1404,6 +1404,8 @@ int work_slot(const std::string& eqn) {
   if (eqn == "Y") return 1;
   if (eqn == "E") return 2;
   if (eqn == "p") return 3;
+  if (eqn == "epsilon") return 4;   // 4, 5: Ctx::work_ras
+  if (eqn == "k") return 5;
   throw Error("dfmi: unknown equation '" + eqn + "'");
 }
 
@@ -1428,7 +1430,10 @@ void record_stats(Ctx& x, const char* eqn, const double* scal, int nsys, const d
   auto& sn = x.stat_snap[eqn];
   sn.h.ensure_mapped((size_t)nsys * NSCAL);
   sn.nsys = nsys;
-  hipLaunchKernelGGL(k_accum_iters, dim3(1), dim3(64), 0, x.stream, scal, nsys, x.work.p + work_slot(eqn), sn.h.d, flag);
+  const int slot = work_slot(eqn);
+  if (slot >= 4 && x.work_ras.n == 0) { x.work_ras.alloc(2); x.work_ras.zero(x.stream); }
+  hipLaunchKernelGGL(k_accum_iters, dim3(1), dim3(64), 0, x.stream, scal, nsys, slot < 4 ? x.work.p + slot : x.work_ras.p + (slot - 4),
+                     sn.h.d, flag);
 }
 
 }  // namespace
@@ -1798,12 +1803,13 @@ void bicg_rows_get(Ctx& x, int nsys, const std::string& part, double* host, long
 
 double solver_work(Ctx& x, const std::string& eqn, bool reset) {
   const int k = work_slot(eqn);
-  if (x.work.n == 0) return 0.0;
+  if ((k < 4 ? x.work.n : x.work_ras.n) == 0) return 0.0;
+  double* at = k < 4 ? x.work.p + k : x.work_ras.p + (k - 4);
   double v = 0.0;
-  DFMI_HIP(hipMemcpyAsync(&v, x.work.p + k, sizeof(double), hipMemcpyDeviceToHost, x.stream));
+  DFMI_HIP(hipMemcpyAsync(&v, at, sizeof(double), hipMemcpyDeviceToHost, x.stream));
   DFMI_HIP(hipStreamSynchronize(x.stream));
   if (reset) {
-    DFMI_HIP(hipMemsetAsync(x.work.p + k, 0, sizeof(double), x.stream));
+    DFMI_HIP(hipMemsetAsync(at, 0, sizeof(double), x.stream));
     DFMI_HIP(hipStreamSynchronize(x.stream));
   }
   return v;

@@ -73,6 +73,26 @@ def read_boundary(path: str) -> dict:
     return out
 
 
+# Patch types of 0/k, 0/epsilon and 0/nut (RAS k-epsilon): kqRWallFunction is zeroGradient by definition;
+# the wall functions proper and the turbulent inlets are not implemented and are refused by name.
+_TURBULENCE_REFUSED = ("epsilonWallFunction", "turbulentMixingLengthDissipationRateInlet", "turbulentIntensityKineticEnergyInlet")
+
+
+def turbulence_patch_types(field: str, types: dict) -> dict:
+    """{patch: type name} of a k, epsilon or nut file (read_field's second result) with kqRWallFunction mapped to
+    zeroGradient; epsilonWallFunction, the nut*WallFunction family and the turbulent inlet conditions raise a ValueError
+    that names the field, the patch and the type"""
+    out = {}
+    for patch, t in types.items():
+        if t == "kqRWallFunction":
+            t = "zeroGradient"
+        elif t in _TURBULENCE_REFUSED or (t.startswith("nut") and t.endswith("WallFunction")):
+            raise ValueError(f"{field}: patch {patch}: boundary condition {t} is not supported "
+                             "(wall functions and turbulent inlet conditions are not implemented)")
+        out[patch] = t
+    return out
+
+
 def write_field(path: str, name: str, values: np.ndarray, patch_types: dict, dims="[0 0 0 0 0 0 0]"):
     vector = values.ndim == 2
     cls = "volVectorField" if vector else "volScalarField"

@@ -11,6 +11,8 @@ EEqn.H fvc::div(phi, K) and fvc::div(hDiffCorrFlux)). dfmi_set_scheme (include/d
 from __future__ import annotations
 
 TERMS = ("div(phi,Yi_h)", "div(phi,K)", "div(hDiffCorrFlux)", "div(phi,U)")
+# the convection of the RAS model's transported scalars (k-epsilon; include/dfmi.h): upwind by default
+RAS_TERMS = ("div(phi,k)", "div(phi,epsilon)")
 UPWIND, LINEAR, LIMITED_LINEAR, LIMITED_LINEAR01, CUBIC, LIMITED_LINEAR_V = 0, 1, 2, 3, 4, 5
 DEFAULT = {"div(phi,Yi_h)": "upwind", "div(phi,K)": "linear", "div(hDiffCorrFlux)": "linear", "div(phi,U)": "linear"}
 # the reference cases' own divSchemes for these terms
@@ -18,13 +20,14 @@ REFERENCE_CASE = {"div(phi,Yi_h)": "limitedLinear01 1", "div(phi,K)": "limitedLi
                   "div(hDiffCorrFlux)": "cubic"}
 _ALLOWED = {"div(phi,Yi_h)": (UPWIND, LIMITED_LINEAR, LIMITED_LINEAR01),
             "div(phi,K)": (UPWIND, LINEAR, LIMITED_LINEAR, LIMITED_LINEAR01),
-            "div(hDiffCorrFlux)": (LINEAR, CUBIC), "div(phi,U)": (LINEAR, LIMITED_LINEAR_V)}
+            "div(hDiffCorrFlux)": (LINEAR, CUBIC), "div(phi,U)": (LINEAR, LIMITED_LINEAR_V),
+            "div(phi,k)": (UPWIND, LINEAR, LIMITED_LINEAR), "div(phi,epsilon)": (UPWIND, LINEAR, LIMITED_LINEAR)}
 
 
 def parse(term: str, scheme: str) -> tuple[int, float]:
     """'limitedLinear01 1' -> (LIMITED_LINEAR01, 1.0); a leading 'Gauss' is accepted"""
-    if term not in TERMS:
-        raise ValueError(f"unknown scheme term {term!r}; expected one of {TERMS}")
+    if term not in TERMS + RAS_TERMS:
+        raise ValueError(f"unknown scheme term {term!r}; expected one of {TERMS + RAS_TERMS}")
     tok = scheme.split()
     if tok and tok[0] == "Gauss":
         tok = tok[1:]
@@ -48,11 +51,13 @@ def parse(term: str, scheme: str) -> tuple[int, float]:
 
 
 def scheme_codes(schemes: dict) -> tuple[list, list]:
-    """{term: scheme} -> (codes[4], k[3]) in TERMS order (k of Yi_h, K, U), defaults filled in"""
+    """{term: scheme} -> (codes[4], k[3]) in TERMS order (k of Yi_h, K, U), defaults filled in; the RAS_TERMS are
+    checked and left out (they are not among the four)"""
     full = dict(DEFAULT)
     for t, v in schemes.items():
         parse(t, v)
-        full[t] = v
+        if t in TERMS:
+            full[t] = v
     codes, ks = [], [1.0, 1.0, 1.0]
     kslot = {0: 0, 1: 1, 3: 2}
     for i, t in enumerate(TERMS):
@@ -120,9 +125,10 @@ def _block(txt: str, name: str):
     return txt[mo.end():i - 1]
 
 
-def read_fv_schemes(path: str) -> dict:
+def read_fv_schemes(path: str, ras: bool = False) -> dict:
     """the entries of a case's system/fvSchemes that dfmi_set_scheme selects ({term: scheme}): the divSchemes entries
-    for TERMS, and 'laplacian' from laplacianSchemes { default ...; } when it is not the default 'orthogonal'. A per-term laplacian entry that differs from
+    for TERMS (with ras=True, a RAS case, also those for RAS_TERMS: laminar and LES cases carry div(phi,k) and
+    div(phi,epsilon) entries that nothing reads), and 'laplacian' from laplacianSchemes { default ...; } when it is not the default 'orthogonal'. A per-term laplacian entry that differs from
     the default (or per-term entries that differ from each other, without a default) is an error: the library runs
     one laplacian scheme."""
     import re
@@ -132,7 +138,7 @@ def read_fv_schemes(path: str) -> dict:
     out = {}
     div = _block(txt, "divSchemes")
     if div is not None:
-        out.update({k: v for k, v in dict_entries(div) if k in TERMS})
+        out.update({k: v for k, v in dict_entries(div) if k in (TERMS + RAS_TERMS if ras else TERMS)})
     lap = _block(txt, "laplacianSchemes")
     if lap is not None:
         entries = dict_entries(lap)

@@ -1,12 +1,15 @@
-"""LES eddy viscosity: the host side of `turbulence->` (dfLowMachFoam.C:207, :508; include/dfmi.h
+"""LES eddy viscosity and RAS k-epsilon: the host side of `turbulence->` (dfLowMachFoam.C:207, :508; include/dfmi.h
 dfmi_turbulence_correct).
 
 The eddy viscosity itself is formed on the device. This module reads a case's constant/turbulenceProperties (and Sct
 from the chemistry dictionary, createFields.H:133), computes the filter width `delta` on the host as OpenFOAM-7's
 cubeRootVolDelta does, and sets the options and fields of a context.
 
-Supported: simulationType laminar | LES; LESModel Smagorinsky | WALE; delta cubeRootVol. Everything else (RAS, the
-dynamic models, Sigma, the other delta types) is refused by name: DESIGN.md 10.
+Supported: simulationType laminar | LES; LESModel Smagorinsky | WALE; delta cubeRootVol. Everything else (the
+dynamic models, Sigma, the other delta types) is refused by name: DESIGN.md 10. parse_turbulence_properties reads the
+laminar and LES files and refuses RAS; parse_ras_properties reads simulationType RAS with RASModel kEpsilon (DESIGN.md
+14) and refuses RNGkEpsilon, every other RASModel and `turbulence off` by name; read_case_turbulence reads
+simulationType and hands the file to one or the other.
 """
 from __future__ import annotations
 
@@ -165,3 +168,95 @@ def apply(ctx, m, settings: dict, nut_patch_types=None) -> None:
     if nut_patch_types is not None:
         ctx.set_patch_types("nut", nut_patch_types)
     ctx.set_field("delta", cube_root_vol_delta(m, settings["deltaCoeff"]))
+
+
+# ------------------------------------------------------------------------------------------------ RAS k-epsilon
+RAS_MODELS = {"kEpsilon": 1}
+# OpenFOAM-7 kEpsilon defaults; kMin / epsilonMin are the model's bounds (SMALL^... of RASModel: 1e-15 here, dfmi.h)
+RAS_DEFAULTS = {"Cmu": 0.09, "C1": 1.44, "C2": 1.92, "C3": 0.0, "sigmak": 1.0, "sigmaEps": 1.3, "kMin": 1e-15,
+                "epsilonMin": 1e-15, "Prt": 1.0, "Sct": 1.0}
+_RAS_COEFFS = ("Cmu", "C1", "C2", "C3", "sigmak", "sigmaEps")
+
+
+def parse_ras_properties(txt: str, chemistry_txt: str | None = None) -> dict:
+    """{"model": 0, "ras_model": 1, "RASModel": "kEpsilon", "Cmu", "C1", "C2", "C3", "sigmak", "sigmaEps", "kMin",
+    "epsilonMin", "Prt", "Sct"} from `simulationType RAS; RAS { RASModel kEpsilon; turbulence on; Prt ...;
+    kEpsilonCoeffs { ... } }` and, for Sct, the chemistry dictionary. "model" is the LES model (0)."""
+    txt = _strip(txt)
+    sim = dict(dict_entries(txt)).get("simulationType")
+    if sim is None:
+        raise ValueError("turbulenceProperties: no simulationType entry")
+    if sim != "RAS":
+        raise ValueError(f"turbulenceProperties: simulationType {sim} is not RAS")
+    out = dict(RAS_DEFAULTS, model=0, ras_model=1, RASModel="kEpsilon")
+    if chemistry_txt is not None:
+        chem = dict(dict_entries(_strip(chemistry_txt)))
+        if "Sct" in chem:
+            out["Sct"] = _number("chemistry dictionary", "Sct", chem["Sct"])
+    ras = sub_dict(txt, "RAS")
+    if ras is None:
+        raise ValueError("turbulenceProperties: simulationType RAS without a RAS sub-dictionary")
+    ent = dict(dict_entries(ras))
+    name = ent.get("RASModel")
+    if name is None:
+        raise ValueError("turbulenceProperties: RAS has no RASModel entry")
+    if name not in RAS_MODELS:
+        raise ValueError(f"turbulenceProperties: RASModel {name} is not supported ({', '.join(RAS_MODELS)})")
+    if ent.get("turbulence", "on") not in ("on", "yes", "true"):
+        raise ValueError(f"turbulenceProperties: RAS turbulence {ent['turbulence']} is not supported (on)")
+    if "Prt" in ent:
+        out["Prt"] = _number("turbulenceProperties RAS", "Prt", ent["Prt"])
+    for k, v in dict_entries(sub_dict(ras, name + "Coeffs") or ""):
+        if k == "C3":
+            try:
+                out[k] = float(v)
+            except ValueError:
+                raise ValueError(f"turbulenceProperties {name}Coeffs: C3 {v!r} is not a number") from None
+            if not np.isfinite(out[k]):
+                raise ValueError(f"turbulenceProperties {name}Coeffs: C3 {v} must be finite")
+        elif k in _RAS_COEFFS or k == "Prt":
+            out[k] = _number(f"turbulenceProperties {name}Coeffs", k, v)
+        else:
+            raise ValueError(f"turbulenceProperties: {name}Coeffs entry {k} is not supported ({', '.join(_RAS_COEFFS)})")
+    return out
+
+
+def read_ras_properties(path: str, chemistry_path: str | None = None) -> dict:
+    """parse_ras_properties of a case's constant/turbulenceProperties (and chemistry dictionary)"""
+    with open(path) as f:
+        txt = f.read()
+    chem = None
+    if chemistry_path is not None:
+        with open(chemistry_path) as f:
+            chem = f.read()
+    return parse_ras_properties(txt, chem)
+
+
+def read_case_turbulence(path: str, chemistry_path: str | None = None) -> dict:
+    """the settings of a case's constant/turbulenceProperties whatever its simulationType: laminar and LES through
+    read_turbulence_properties, RAS through read_ras_properties (its result has "RASModel")"""
+    with open(path) as f:
+        sim = dict(dict_entries(_strip(f.read()))).get("simulationType")
+    if sim == "RAS":
+        return read_ras_properties(path, chemistry_path)
+    return read_turbulence_properties(path, chemistry_path)
+
+
+def apply_ras(ctx, m, settings: dict, patch_types: dict | None = None, k=None, epsilon=None) -> None:
+    """the options ras.* on a context that has been set up (case.setup_context), the patch types of "k", "epsilon" and
+    "nut" where patch_types has them, and, where given, the cell fields k and epsilon with boundary values as
+    correctBoundaryConditions would leave them (zeroGradient / coupled; fixed-value slots are the caller's to set).
+    settings: parse_ras_properties' result."""
+    from . import case
+    ctx.set_option("les.model", 0)
+    for key in ("Cmu", "C1", "C2", "C3", "sigmak", "sigmaEps", "kMin", "epsilonMin", "Prt", "Sct"):
+        ctx.set_option("ras." + key, settings[key])
+    ctx.set_option("ras.model", settings.get("ras_model", 1))
+    for f in ("k", "epsilon", "nut"):
+        if patch_types is not None and patch_types.get(f) is not None:
+            ctx.set_patch_types(f, patch_types[f])
+    for name, v in (("k", k), ("epsilon", epsilon)):
+        if v is not None:
+            v = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (m.n_cells,)))
+            ctx.set_field(name, v)
+            ctx.set_field("boundary_" + name, case.boundary_values(m, v).reshape(-1))

@@ -150,7 +150,7 @@ int dfmi_set_traversal(dfmi_ctx* ctx, const int* order);
 /* ---- per-equation patch types ------------------------------------------------------------ */
 /* dfUEqn/dfYEqn/dfEEqn/dfpEqn/dfRhoEqn/dfThermo::setConstantFields (e.g. dfUEqn.cu:364-379,
  * dfEEqn.cu setConstantFields, dfThermo.cu setConstantFields). field in
- * {"U","p","he","K","Y","T","rho","nut"}; patch_type[num_patches]. "nut" (LES, below) takes zeroGradient, fixedValue,
+ * {"U","p","he","K","Y","T","rho","nut","k","epsilon"}; patch_type[num_patches]. "nut" (LES / RAS, below) takes zeroGradient, fixedValue,
  * calculated, cyclic, processor, processorCyclic and empty; not set, it is "calculated" on every non-coupled patch
  * (OpenFOAM's default for nut: the stored boundary_nut is kept, zero unless set) */
 int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* patch_type);
@@ -173,7 +173,8 @@ int dfmi_thermo_load(dfmi_ctx* ctx, const char* thermo_coeff_file);
  *        boundary_<name> for the boundary counterparts; boundary-only: boundary_heGradient,
  *        boundary_{U,p,Y,K}_ref (inletOutlet inletValue), boundary_p_vf (waveTransmissive valueFraction),
  *        boundary_p_gamma, chem_stats [3][C]. count = values per component.
- *        LES: delta (cells; positive), nut (cells; get only), boundary_nut (set: the fixedValue / calculated slots). */
+ *        LES: delta (cells; positive), nut (cells; get only), boundary_nut (set: the fixedValue / calculated slots).
+ *        RAS: k epsilon (cells), boundary_{k,epsilon}, boundary_{k,epsilon}_ref; get only: G divU k_prebound epsilon_prebound. */
 int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long count, int layout);
 int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, int layout);
 
@@ -201,7 +202,47 @@ int dfmi_E_process(dfmi_ctx* ctx);              /* dfEEqn::process (dfEEqn.cu:10
  * simulationType != laminar: fvmDiv(phiUc, Yi) (YEqn.H:101-106), diffAlphaD and div(hDiffCorrFlux) (EEqn.H:30-36) --
  * the YEqn preparation kernel is not launched and sumYDiffError, hDiffCorrFlux, diffAlphaD, phiUc read back as zeros.
  * dfmi_U_process / dfmi_Y_process / dfmi_E_process / dfmi_assemble use the nut in the context and fail when it is not
- * valid. les.model = 0: a successful no-op. */
+ * valid. les.model = 0: a successful no-op.
+ *
+ * ---- RAS k-epsilon (ras.model = 1): the same call is kEpsilon::correct(). The statement below is the definition: it
+ * restates OpenFOAM-7 kEpsilon::correct() / correctNut() and bound() for the compressible solver (alpha = 1, no
+ * fvOptions, no wall functions). Options (dfmi_set_option; all positive and finite, C3 any finite value):
+ *   ras.model  0 none (default) | 1 kEpsilon          (ras.model != 0 together with les.model != 0 is refused)
+ *   ras.Cmu 0.09, ras.C1 1.44, ras.C2 1.92, ras.C3 0, ras.sigmak 1.0, ras.sigmaEps 1.3,
+ *   ras.kMin 1e-15, ras.epsilonMin 1e-15, ras.Prt 1, ras.Sct 1     (Prt / Sct replace les.Prt / les.Sct in RAS mode)
+ * g = grad(U) is the UEqn's Gauss linear gradient (the same faces in the same order), nut the old value, mu the thermo's:
+ *   divU  = (1/V) [ sum_f +-phi_f / interp_f(w, rho_P, rho_N)  +  sum_slots boundary_phi / boundary_rho ]
+ *           (a coupled slot's boundary_rho is the face interpolate w rho_c + (1 - w) rho_neighbour)
+ *   G     = nut (dev(twoSymm(g)) && g)                 T = g + g^T, t3 = (1/3) tr T,
+ *           ((T00-t3) g00 + (T11-t3) g11 + (T22-t3) g22) + ((T01 g01 + T01 g10) + (T02 g02 + T02 g20) + (T12 g12 + T12 g21))
+ *   Dk    = rho (nut/sigmak + mu/rho)        Deps = rho (nut/sigmaEps + mu/rho)     (cells and slots alike)
+ *   epsEqn:  ddt(rho,eps) + div(phi,eps) - laplacian(Deps,eps)
+ *              == C1 rho G eps/k  - SuSp((2/3 C1 - C3) rho divU, eps)  - Sp(C2 rho eps/k, eps)
+ *            solve;  bound(eps, epsilonMin)
+ *   kEqn:    ddt(rho,k) + div(phi,k) - laplacian(Dk,k)
+ *              == rho G  - SuSp(2/3 rho divU, k)  - Sp(rho eps/k, k)          (eps: the new one; k in eps/k: the old one)
+ *            solve;  bound(k, kMin)
+ *   nut = Cmu k^2 / eps;   boundary_nut by nut's patch types (calculated slots: Cmu boundary_k^2 / boundary_epsilon);   halo
+ * ddt is Euler with rho_old and the field's own start-of-call value (k_old / epsilon_old are not part of
+ * dfmi_pre_time_step). SuSp(a, psi) is diag += V max(a,0), source -= V min(a,0) psi; Sp(b, psi) is diag += V b. Per cell
+ *   diag = ((rdt rho V + d1) - dL) + V Sp,  source = rdt rho_old psi V + V Su      (d1 convection, dL laplacian, as the EEqn)
+ * div(phi,k) / div(phi,epsilon): dfmi_set_scheme, upwind (default) | limitedLinear <k> | linear. The laplacians go through
+ * the laplacian scheme in force; under "corrected" the explicit term is added from the field's Gauss gradient. Boundary
+ * coefficients as the EEqn's for zeroGradient, fixedValue, inletOutlet (boundary_{k,epsilon}_ref), cyclic, processor,
+ * processorCyclic, calculated and empty. bound(psi, m) applies to every cell of the solved field psi (its slots corrected):
+ *   psi = max(max(psi, avg(max(psi,m)) * pos0(-psi)), m),  avg = sum_f |Sf| interp_f / sum_f |Sf| over the cell's faces and
+ *   slots (a coupled slot -- cyclic, processor -- is a face: the interpolate of the two bounded cell values, so the result
+ *   does not depend on a decomposition; every other slot max(boundary_psi, m)); then every slot: boundary_psi = max(boundary_psi, m).
+ * Applied unconditionally it equals OpenFOAM's gated form (the gate is the global minimum): a field >= m is unchanged bitwise.
+ * Which rho: the one dfLowMachFoam.C:508 sees -- after the last pEqn.H (its correctPsipRho and rhoEqn: rho += psi p - psip0,
+ * then the rhoEqn from rho_old and the final phi), before rho = thermo.rho() (:517); rho_old and phi are the step's.
+ * dfmi_time_step in RAS mode runs that corrector tail (laminar / LES skip it: nothing reads it) and this call before the
+ * final rho = psi p. Fields: k, epsilon, boundary_k, boundary_epsilon (set / get; all four must have been set: an error
+ * names the missing one), G, divU, k_prebound, epsilon_prebound (get only: production, dilatation, and the solved fields
+ * before bound()); patch types "k" and "epsilon". nut belongs to k and epsilon: writing either, a boundary counterpart,
+ * ras.model or a coefficient invalidates it; dfmi_time_step and the per-equation entries then run correctNut() only
+ * (turbulence->validate()), never the equations. Solver names "epsilon" and "k" (dfmi_set_solver / _stats / _work);
+ * dfmi_assemble / dfmi_get_matrix take "epsilon" and "k": each is formed from the fields as they stand, no solve between. */
 int dfmi_turbulence_correct(dfmi_ctx* ctx);
 int dfmi_thermo_correct(dfmi_ctx* ctx);         /* dfThermo::correctThermo (dfThermo.cu:572-671) */
 int dfmi_thermo_update_energy(dfmi_ctx* ctx);   /* he, psi, rho, transport from T (dfThermo::updateEnergy) */
@@ -256,7 +297,7 @@ int dfmi_hbm_copy_peak(dfmi_ctx* ctx, double gib, int reps, double* gbs);
 int dfmi_correct_boundary(dfmi_ctx* ctx, const char* field);
 
 /* ---- matrix inspection (the reference DEBUG_CHECK_LDU / compareResult path, dfYEqn.cu:566-572) */
-/* eqn in {"rho","U","Y","E","p","HbyA","Y_ell","Y_ell_ref"}: run that equation's assembly only (no solve); under
+/* eqn in {"rho","U","Y","E","p","HbyA","Y_ell","Y_ell_ref","epsilon","k"}: run that equation's assembly only (no solve); under
  * the laplacian scheme "corrected" the sources include the explicit term ("p": that of the corrector loop's first pass) */
 int dfmi_assemble(dfmi_ctx* ctx, const char* eqn);
 /* part in {"lower","upper","diag","source","source_solve","internal_coeffs","boundary_coeffs"} */
@@ -267,7 +308,7 @@ int dfmi_get_matrix(dfmi_ctx* ctx, const char* eqn, const char* part, double* ho
  * part "val" [S-1][W][C] (W = coupling entries per row), "dS" (diag + internalCoeffs) or "rhs"
  * [S-1][C]. eqn must be "Y". */
 int dfmi_get_solver_rows(dfmi_ctx* ctx, const char* eqn, const char* part, double* host, long count);
-/* solver controls (amgxUOptions / amgxpOptions): eqn in {"U","Y","E","p"} */
+/* solver controls (amgxUOptions / amgxpOptions): eqn in {"U","Y","E","p","epsilon","k"} */
 int dfmi_set_solver(dfmi_ctx* ctx, const char* eqn, int max_iter, double tol, double abs_tol);
 /* preconditioner: "jacobi" (all) or "amg" (p; aggregation AMG V-cycle, the amgxpOptions
  * AGGREGATION solver's role) -- p defaults to "amg", U/Y/E to "jacobi" */
@@ -281,6 +322,7 @@ int dfmi_set_preconditioner(dfmi_ctx* ctx, const char* eqn, const char* name);
  * "solver.*" (even_odd, small, row_classes), "pcg.*" (face_form, fuse_l0), "fv.*" (hex_walk, csr_walk,
  * species_generic, yprep_brick), "chem.*" (method 0 ROS3 | 1 extrapolation, generated, binning),
  * "les.*" (model, Ck, Ce, Cw, Prt, Sct: dfmi_turbulence_correct above),
+ * "ras.*" (model, Cmu, C1, C2, C3, sigmak, sigmaEps, kMin, epsilonMin, Prt, Sct: the same call's RAS block),
  * "dnn.tuned_gemm", "step.courant" (1: dfmi_time_step queues the Courant-number kernel behind its last
  * kernel and posts the result to pinned memory for dfmi_courant_no; 0, the default: nothing added); keys and
  * defaults in INTEGRATION.md. Solver-structure keys must be set before the first solve; unknown keys fail. */
