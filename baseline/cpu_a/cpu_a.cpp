@@ -102,6 +102,11 @@ struct Ctx {
   std::map<std::string, double> ras = {{"ras.model", 0}, {"ras.Cmu", 0.09}, {"ras.C1", 1.44}, {"ras.C2", 1.92}, {"ras.C3", 0.0},
                                        {"ras.sigmak", 1.0}, {"ras.sigmaEps", 1.3}, {"ras.kMin", 1e-15}, {"ras.epsilonMin", 1e-15},
                                        {"ras.Prt", 1.0}, {"ras.Sct", 1.0}};
+  // combustion closure (options tci.*): the keys and defaults of the HIP library, accepted and kept; tci.model != 0 is refused by name
+  std::map<std::string, double> tci = {{"tci.model", 0}, {"tci.mixing", 1}, {"tci.chemistry", 1}, {"tci.Cmix", 0.1}, {"tci.fuel", -1},
+                                       {"tci.oxidizer", -1}, {"tci.CO2", -1}, {"tci.H2", -1}, {"tci.version", 2005},
+                                       {"tci.C1", 0.05774}, {"tci.C2", 0.5}, {"tci.Cgamma", 2.1377}, {"tci.Ctau", 0.4083},
+                                       {"tci.exp1", 0}, {"tci.exp2", 0}, {"tci.bad_tauStar", 0}};
   struct Les { int model = 0; double Ck = 0.094, Ce = 1.048, Cw = 0.325, Prt = 1.0, Sct = 1.0; bool valid = false, have_delta = false; } les;
   bool step_courant = false;   // option step.courant: accepted for the callers that set it; the number is always computed on demand
   bool have_sizes = false, have_topo = false, have_geom = false, have_bgeom = false;
@@ -1284,6 +1289,27 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
       *slot = value;
       return;
     }
+    if (ctx && key && std::string(key).rfind("tci.", 0) == 0) {   // the keys of the HIP library; the closures are its alone
+      const std::string k(key);
+      auto it = ctx->x.tci.find(k);
+      CHECK(it != ctx->x.tci.end(), "unknown option '" + k + "'");
+      const auto one_of = [&](std::initializer_list<double> vs) { bool ok = false; for (double v : vs) ok |= value == v; return ok; };
+      CHECK(k != "tci.bad_tauStar", "tci.bad_tauStar is a counter and cannot be set");
+      if (k == "tci.model") {
+        CHECK(one_of({0, 1, 2}), "tci.model must be 0 (none), 1 (PaSR) or 2 (EDC)");
+        CHECK(value == 0.0, "tci.model != 0: CPU-A does not implement the PaSR / EDC closures (the HIP library)");
+      } else if (k == "tci.mixing") {
+        CHECK(value != 4.0, "tci.mixing dynamicScale is not supported");
+        CHECK(one_of({1, 2, 3}), "tci.mixing must be 1 (globalScale), 2 (kolmogorovScale) or 3 (geometriMeanScale)");
+      } else if (k == "tci.chemistry") CHECK(one_of({1, 2, 3}), "tci.chemistry must be 1 (globalConvertion), 2 (formationRate) or 3 (reactionRate)");
+      else if (k == "tci.version") CHECK(one_of({1981, 1996, 2005, 2016}), "tci.version must be 1981, 1996, 2005 or 2016");
+      else if (k == "tci.exp1" || k == "tci.exp2") CHECK(one_of({0, 1, 2, 3, 4}), k + " must be 0 (the version's own) or an integer 1..4");
+      else if (k == "tci.fuel" || k == "tci.oxidizer" || k == "tci.CO2" || k == "tci.H2")
+        CHECK(value >= -1 && value < 64 && value == (double)(int)value, k + " must be a species index, or -1 (not considered)");
+      else CHECK(value > 0 && value <= 1.79769313486231570e308, k + " must be positive and finite");
+      it->second = value;
+      return;
+    }
     if (ctx && key && std::string(key).rfind("ras.", 0) == 0) {   // the keys of the HIP library; the model itself is its alone
       const std::string k(key);
       auto it = ctx->x.ras.find(k);
@@ -1309,6 +1335,12 @@ int dfmi_get_option(dfmi_ctx* ctx, const char* key, double* value) {
       const double* slot = k == "les.Ck" ? &q.Ck : k == "les.Ce" ? &q.Ce : k == "les.Cw" ? &q.Cw : k == "les.Prt" ? &q.Prt : k == "les.Sct" ? &q.Sct : nullptr;
       CHECK(slot, "unknown option '" + k + "'");
       *value = *slot;
+      return;
+    }
+    if (ctx && key && value && std::string(key).rfind("tci.", 0) == 0) {
+      auto it = ctx->x.tci.find(key);
+      CHECK(it != ctx->x.tci.end(), std::string("unknown option '") + key + "'");
+      *value = it->second;
       return;
     }
     if (ctx && key && value && std::string(key).rfind("ras.", 0) == 0) {
@@ -1426,6 +1458,10 @@ int dfmi_chem_set_options(dfmi_ctx* ctx, int mode, double rtol, double atol, dou
   });
 }
 int dfmi_chem_solve(dfmi_ctx* ctx, double dt) {
+  return guard([&] { require_ready(ctx->x); CHECK(dt > 0, "dt must be positive"); chem_solve(ctx->x, dt, "rho"); });
+}
+// combustion->correct(): tci.model is always 0 here, so this is the solve
+int dfmi_combustion_correct(dfmi_ctx* ctx, double dt) {
   return guard([&] { require_ready(ctx->x); CHECK(dt > 0, "dt must be positive"); chem_solve(ctx->x, dt, "rho"); });
 }
 int dfmi_chem_set_max_steps(dfmi_ctx* ctx, int n) { return guard([&] { CHECK(n > 0, "max_steps must be positive"); ctx->x.max_steps = n; }); }

@@ -118,6 +118,10 @@ void ensure_ras_fields(Ctx& x) {
   A.ic.zero(x.stream); A.bc.zero(x.stream);
   for (auto e : {"k", "epsilon"}) if (!x.solver.count(e)) x.solver[e] = SolverCfg{20, 1e-5, 0.0};
 }
+bool tci_name(const std::string& n) {
+  for (const char* s : {"tci_kappa", "tci_tmix", "tci_tauStar", "tci_tc", "RR_eff", "Qdot_eff"}) if (n == s) return true;
+  return false;
+}
 bool ras_name(const std::string& n) {
   static const char* names[] = {"k", "epsilon", "boundary_k", "boundary_epsilon", "G", "divU", "k_prebound", "epsilon_prebound",
                                 "boundary_k_prebound", "boundary_epsilon_prebound", "boundary_k_ref", "boundary_epsilon_ref"};
@@ -266,7 +270,8 @@ void do_Y_front(Ctx& x, bool weights = true, hipEvent_t rows_after = nullptr) {
   YWs _yw(x);
   // chemistry->solve(deltaT) before YEqn (YEqn.H); the thermo density of that call is rho before this
   // step's rhoEqn, i.e. rho_old (dfChemistryModel.C:87,771; the GPU reference passes d_rho_old, dfYEqn.cu:449)
-  if (x.chem.mode == 1) chem_solve(x, 1.0 / x.rdt, "rho_old");
+  // (combustion->correct(), YEqn.H:76: with a closure in force -- options tci.* -- the solve, kappa and the scaled source)
+  if (x.chem.mode == 1) combustion_correct(x, 1.0 / x.rdt, "rho_old");
   else if (x.chem.mode == 2) dnn_solve(x, "rho_old");   // chemistrySolver_GPU.Inference (YEqn_GPU.H)
   y_prep(x, weights);
   if (rows_after) DFMI_HIP(hipStreamWaitEvent(x.stream, rows_after, 0));
@@ -792,6 +797,10 @@ int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long cou
     const std::string n(name ? name : "");
     if (n == "delta" || n == "nut" || n == "boundary_nut") ensure_les_fields(x);
     if (ras_name(n)) ensure_ras_fields(x);
+    if (tci_name(n)) {
+      DFMI_CHECK(n == "tci_tc", "field '" + n + "' is formed by dfmi_combustion_correct and cannot be set");
+      ensure_tci_fields(x);
+    }
     DFMI_CHECK(n != "G" && n != "divU" && n.find("_prebound") == std::string::npos,
                "field '" + n + "' is formed by dfmi_turbulence_correct and cannot be set");
     DFMI_CHECK(n != "nut", "field 'nut' is formed by dfmi_turbulence_correct and cannot be set (boundary_nut holds the fixed-value slots)");
@@ -818,6 +827,7 @@ int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, in
     const std::string n(name ? name : "");
     if (n == "delta" || n == "nut" || n == "boundary_nut") ensure_les_fields(ctx->x);
     if (ras_name(n)) ensure_ras_fields(ctx->x);
+    if (tci_name(n)) ensure_tci_fields(ctx->x);
     copy_field(ctx->x, n, host, count, layout, false);
   });
 }
@@ -1123,6 +1133,7 @@ int dfmi_assemble(dfmi_ctx* ctx, const char* eqn) {
       // corrected laplacian: the source of the corrector loop's first pass (do_p_nonorth)
       if (x.lap == LAP_CORRECTED) { nonorth_p_base(x); nonorth_p_correct(x); }
     }
+    else if (e == "tci") combustion_pointwise(x);   // the closure's pointwise passes from RR and Qdot as they stand
     else if (e == "HbyA") u_hbya(x);
     else if (e == "p_post") p_post_solve(x);
     else if (e == "Y_post") y_post_solve(x);
@@ -1188,6 +1199,7 @@ int dfmi_chem_set_options(dfmi_ctx* ctx, int mode, double rtol, double atol, dou
   return guard([&] {
     DFMI_CHECK(mode >= 0 && mode <= 2, "chemistry mode must be 0 (off), 1 (ODE) or 2 (DNN)");
     DFMI_CHECK(rtol > 0 && atol > 0, "chemistry tolerances must be positive");
+    DFMI_CHECK(mode != 2 || !ctx->x.tci.model, "chemistry mode 2 (DNN) is not available with tci.model != 0");
     Chem& c = ctx->x.chem;
     c.mode = mode; c.rtol = rtol; c.atol = atol; c.Tmin = T_min;
   });
@@ -1295,6 +1307,19 @@ int dfmi_chem_solve(dfmi_ctx* ctx, double dt) {
   });
 }
 
+// combustion->correct() (YEqn.H:76; PaSR.C:205-396, EDC.C:83-171)
+int dfmi_combustion_correct(dfmi_ctx* ctx, double dt) {
+  return guard([&] {
+    DFMI_CHECK(ctx, "null context");
+    Ctx& x = ctx->x;
+    require_ready(x);
+    DFMI_CHECK(dt > 0, "chemistry time step must be positive");
+    combustion_correct(x, dt, "rho");
+    DFMI_HIP(hipStreamSynchronize(x.stream));
+    chem_check(x);
+  });
+}
+
 int dfmi_zero_d_step(dfmi_ctx* ctx, double dt, int n_steps) {
   return guard([&] {
     Ctx& x = ctx->x;
@@ -1397,6 +1422,8 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
       // assembly, but a changed coefficient invalidates all the same: one rule)
       DFMI_CHECK(k != "les.model" || value == 0.0 || !x.ras.model,
                  "dfmi_set_option: les.model != 0 and ras.model != 0 exclude each other (one turbulence model at a time)");
+      DFMI_CHECK(k != "les.model" || value == 0.0 || !x.tci.model,
+                 "dfmi_set_option: les.model != 0 and tci.model != 0 exclude each other");
       if (value != x.opt(key)) { x.les.valid = false; x.les.zeroed = false; }
       if (k == "les.model") x.les.model = (int)value;
       if (x.les.model && x.have_bgeom) ensure_les_fields(x);
@@ -1415,12 +1442,46 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
       if (k == "ras.model") x.ras.model = (int)value;
       if (x.ras.model && x.have_bgeom) ensure_ras_fields(x);
     }
+    if (k.rfind("tci.", 0) == 0) {
+      const auto one_of = [&](std::initializer_list<double> vs) { bool ok = false; for (double v : vs) ok |= value == v; return ok; };
+      DFMI_CHECK(k != "tci.bad_tauStar", "dfmi_set_option: tci.bad_tauStar is a counter and cannot be set");
+      if (k == "tci.model") {
+        DFMI_CHECK(one_of({0, 1, 2}), "dfmi_set_option: tci.model must be 0 (none), 1 (PaSR) or 2 (EDC)");
+        DFMI_CHECK(value == 0.0 || !x.les.model, "dfmi_set_option: tci.model != 0 and les.model != 0 exclude each other");
+        DFMI_CHECK(value == 0.0 || x.chem.mode != 2,
+                   "dfmi_set_option: tci.model != 0 is not available with the DNN surrogate (chemistry mode 2)");
+      } else if (k == "tci.mixing") {
+        DFMI_CHECK(value != 4.0, "dfmi_set_option: tci.mixing dynamicScale is not supported (its Z / Zvar / Chi equations are not on the device)");
+        DFMI_CHECK(one_of({1, 2, 3}), "dfmi_set_option: tci.mixing must be 1 (globalScale), 2 (kolmogorovScale) or 3 (geometriMeanScale)");
+      } else if (k == "tci.chemistry")
+        DFMI_CHECK(one_of({1, 2, 3}), "dfmi_set_option: tci.chemistry must be 1 (globalConvertion), 2 (formationRate) or 3 (reactionRate)");
+      else if (k == "tci.version")
+        DFMI_CHECK(one_of({1981, 1996, 2005, 2016}), "dfmi_set_option: tci.version must be 1981, 1996, 2005 or 2016");
+      else if (k == "tci.exp1" || k == "tci.exp2")
+        DFMI_CHECK(one_of({0, 1, 2, 3, 4}), "dfmi_set_option: " + k + " must be 0 (the version's own) or an integer 1..4");
+      else if (k == "tci.fuel" || k == "tci.oxidizer" || k == "tci.CO2" || k == "tci.H2")
+        DFMI_CHECK(value >= -1 && value < 64 && value == (double)(int)value && (!x.have_sizes || value < x.S),
+                   "dfmi_set_option: " + k + " must be a species index, or -1 (not considered)");
+      else
+        DFMI_CHECK(value > 0 && value <= 1.79769313486231570e308, "dfmi_set_option: " + k + " must be positive and finite");
+      if ((k == "tci.model" || k == "tci.chemistry") && value != x.opt(key)) tci_reset_tc(x);
+      if (k == "tci.model") x.tci.model = (int)value;
+    }
     x.opts[k] = value;
   });
 }
 
 int dfmi_get_option(dfmi_ctx* ctx, const char* key, double* value) {
-  return guard([&] { *value = ctx->x.opt(key); });
+  return guard([&] {
+    Ctx& x = ctx->x;
+    *value = x.opt(key);
+    if (std::string(key) == "tci.bad_tauStar" && x.tci.bad.n) {   // the last EDC correct's count, read back from the device
+      int nb = 0;
+      DFMI_HIP(hipStreamSynchronize(x.stream));
+      DFMI_HIP(hipMemcpy(&nb, x.tci.bad.p, sizeof(int), hipMemcpyDeviceToHost));
+      *value = nb;
+    }
+  });
 }
 
 int dfmi_set_preconditioner(dfmi_ctx* ctx, const char* eqn, const char* name) {

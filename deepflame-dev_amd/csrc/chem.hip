@@ -470,11 +470,20 @@ __device__ __forceinline__ double reactor_state(double T, double p, const double
   return rho;
 }
 
-template <int S>
+// The integration interval of cell c: the launch's one value, or the cell's own (EDC's chemistryPtr_->solve(tauStar),
+// EDC.C:170: the kernels instantiated with DT = const double*). A per-cell interval that is not positive and finite
+// integrates nothing and gives RR = 0; the scalar instantiations fold both helpers away and compile as they always did
+// (profiles/tci_resource_usage.md).
+__device__ __forceinline__ double cell_dt(double dt, long) { return dt; }
+__device__ __forceinline__ __attribute__((unused)) double cell_dt(const double* dt, long c) { return dt[c]; }
+__device__ __forceinline__ constexpr bool dt_live(double, double) { return true; }
+__device__ __forceinline__ __attribute__((unused)) bool dt_live(const double*, double dt) { return dt > 0.0 && dt <= 1.79769313486231570e308; }
+
+template <int S, class DT = double>
 __global__ void __launch_bounds__(LANES) k_chem(long n, const int* __restrict__ perm, ChemMech m,
                                                 const double* __restrict__ Tf, const double* __restrict__ pf,
                                                 const double* __restrict__ rhof, const double* __restrict__ Yf,
-                                                double dt, double rtol, double atol, double Tmin, int max_steps,
+                                                DT dt_in, double rtol, double atol, double Tmin, int max_steps,
                                                 int method, double* __restrict__ RR, double* __restrict__ stats,
                                                 int* __restrict__ fail, int tiled, const double* __restrict__ hc,
                                                 double* __restrict__ Qdot) {
@@ -490,13 +499,14 @@ __global__ void __launch_bounds__(LANES) k_chem(long n, const int* __restrict__ 
   const long c = bin_cell(perm, t);
   if (c >= n) return;
   const double T = Tf[c], rho_rr = rhof[c];
+  const double dt = cell_dt(dt_in, c);
   double Y0[S], y[S];
 #pragma unroll
   for (int i = 0; i < S; ++i) Y0[i] = Yf[(long)i * n + c];
   const double rho = reactor_state<S>(T, pf[c], Y0, m.W, y);
   int steps = 0, rejects = 0;
   double hnext = 0.0;   // the step the integration would take next
-  if (T >= Tmin) {
+  if (T >= Tmin && dt_live(dt_in, dt)) {
     rate_constants<S>(m, L, T);
     double sc[S];
 #pragma unroll
@@ -561,7 +571,7 @@ __global__ void __launch_bounds__(LANES) k_chem(long n, const int* __restrict__ 
 #pragma unroll
   for (int i = 0; i < S; ++i) {
     const double Yn = y[i] * m.W[i] / rho;
-    const double rr = T >= Tmin ? (Yn - Y0[i]) * rho_rr / dt : 0.0;
+    const double rr = T >= Tmin && dt_live(dt_in, dt) ? (Yn - Y0[i]) * rho_rr / dt : 0.0;
     RR[(long)i * n + c] = rr;
     q -= hc[i] * rr;
   }
@@ -611,10 +621,10 @@ struct KLds {
   __device__ __forceinline__ double& operator[](int i) const { return base[i * LANES + lane]; }
 };
 
-template <class G>
+template <class G, class DT = double>
 __global__ void __launch_bounds__(LANES, 1) k_chem_gen(long n, const int* __restrict__ perm,
     const double* __restrict__ Tf, const double* __restrict__ pf, const double* __restrict__ rhof,
-    const double* __restrict__ Yf, double dt, double rtol, double atol, double Tmin, int max_steps,
+    const double* __restrict__ Yf, DT dt_in, double rtol, double atol, double Tmin, int max_steps,
     double* __restrict__ RR, double* __restrict__ stats, int* __restrict__ fail, int tiled, const double* __restrict__ hc,
     double* __restrict__ Qdot) {
   constexpr int S = G::S, SA = G::SA;
@@ -630,6 +640,7 @@ __global__ void __launch_bounds__(LANES, 1) k_chem_gen(long n, const int* __rest
   const long c = bin_cell(perm, t);
   if (c >= n) return;
   const double T = Tf[c];
+  const double dt = cell_dt(dt_in, c);
   double y[S];
   double rho;
   {
@@ -640,7 +651,7 @@ __global__ void __launch_bounds__(LANES, 1) k_chem_gen(long n, const int* __rest
   }
   int steps = 0, rejects = 0;
   double hnext = 0.0;   // the step the integration would take next
-  if (T >= Tmin) {
+  if (T >= Tmin && dt_live(dt_in, dt)) {
     G::consts(T, kh);
     // first step: the size the previous solve of this cell ended with (OpenFOAM's per-cell deltaTChem)
     const double hp = stats[2 * n + c];
@@ -708,7 +719,7 @@ __global__ void __launch_bounds__(LANES, 1) k_chem_gen(long n, const int* __rest
 #pragma unroll
   for (int i = 0; i < S; ++i) {
     const double Yn = y[i] * G::W[i] / rho;
-    const double rr = T >= Tmin ? (Yn - Yf[(long)i * n + c]) * rho_rr / dt : 0.0;
+    const double rr = T >= Tmin && dt_live(dt_in, dt) ? (Yn - Yf[(long)i * n + c]) * rho_rr / dt : 0.0;
     RR[(long)i * n + c] = rr;
     q -= hc[i] * rr;
   }
@@ -855,6 +866,53 @@ template <int TG> struct Coop {
         else if (type >= 2) t = k0[r] / kinf * (F / ((1.0 + Pr) * (1.0 + Pr)) - corr) * (fi - bi);
         tb[r] = t;
       }
+    }
+    cell_sync();
+  }
+
+  // k_tci_rates: the forward and reverse rates of progress at the concentrations in C -- the f and b that reactions()
+  // differences, times the third-body factor -- weighted as PaSR.C:341-371 sums them: wf = sum_products nu_p fwd into ke,
+  // wr = sum_reactants nu_r rev into Mf
+  __device__ __forceinline__ void progress(const ChemMech& m, double T) const {
+    cell_sync();
+    for (int r = l; r < R; r += TG) {
+      const int* id = m.idata + r * 8;
+      const int* ix = m.irs + r * 6;
+      const double* d = m.dd + (long)r * m.ndd;
+      const int type = id[0];
+      const double kinf = kf[r];
+      double k = kinf, mf = 1.0, M = 0.0, F = 1.0, Pr = 0.0;
+      if (type != 0) {
+        for (int i = 0; i < S; ++i) M += d[17 + i] * C[i];
+        if (type == 1) mf = M;
+        else {
+          Pr = k0[r] * M / kinf;
+          if (type == 3) {
+            const double a = d[12], T3 = d[13], T1 = d[14], T2 = d[15];
+            const double Fc = (1 - a) * exp(-T / T3) + a * exp(-T / T1) + (id[4] ? exp(-T2 / T) : 0.0);
+            const double lFc = log10(fmax(Fc, 1e-300));
+            const double c = -0.4 - 0.67 * lFc, n = 0.75 - 1.27 * lFc;
+            const double lPr = log10(fmax(Pr, 1e-300));
+            const double u = n - 0.14 * (lPr + c);
+            const double f1 = (lPr + c) / u;
+            F = exp10(lFc / (1 + f1 * f1));
+          }
+          k = kinf * Pr / (1 + Pr) * F;
+        }
+      }
+      double f = k, b = id[1] ? k * ikc[r] : 0.0;
+      for (int j = 0; j < 3; ++j) {
+        if (ix[j] >= 0) f *= ipow(C[ix[j]], d[3 + j]);
+        if (ix[3 + j] >= 0) b *= ipow(C[ix[3 + j]], d[6 + j]);
+      }
+      const double fwd = mf * f, rev = mf * b;
+      double wf = 0.0, wr = 0.0;
+      for (int j = 0; j < 3; ++j) {
+        if (ix[3 + j] >= 0) wf += d[6 + j] * fwd;
+        if (ix[j] >= 0) wr += d[3 + j] * rev;
+      }
+      ke[r] = wf;
+      Mf[r] = wr;
     }
     cell_sync();
   }
@@ -1016,10 +1074,10 @@ template <int TG, int NCB> __device__ inline long coop_slot(int tiled) {
   return b * NCB + threadIdx.x / TG;
 }
 
-template <int TG, int NCB>
+template <int TG, int NCB, class DT = double>
 __global__ void __launch_bounds__(TG * NCB) k_chem_coop(long n, const int* __restrict__ perm, ChemMech m, CoopList cl, int S,
     const double* __restrict__ Tf, const double* __restrict__ pf, const double* __restrict__ rhof,
-    const double* __restrict__ Yf, double dt, double rtol, double atol, double Tmin, int max_steps,
+    const double* __restrict__ Yf, DT dt_in, double rtol, double atol, double Tmin, int max_steps,
     double* __restrict__ RR, double* __restrict__ stats, int* __restrict__ fail, int tiled, const double* __restrict__ hc,
     double* __restrict__ Qdot) {
   static_assert(LANES % TG == 0 && (TG * NCB) % LANES == 0, "a cell must not straddle waves");
@@ -1045,6 +1103,7 @@ __global__ void __launch_bounds__(TG * NCB) k_chem_coop(long n, const int* __res
   const long c = bin_cell(perm, t);
   if (c >= n) return;
   const double T = Tf[c];
+  const double dt = cell_dt(dt_in, c);
   double y[RPL], Wl[RPL];
   double rho;
   {   // reactor_state (setState_TPY), sums in species order
@@ -1066,7 +1125,7 @@ __global__ void __launch_bounds__(TG * NCB) k_chem_coop(long n, const int* __res
   }
   int steps = 0, rejects = 0;
   double hnext = 0.0;   // the step the integration would take next
-  if (T >= Tmin) {
+  if (T >= Tmin && dt_live(dt_in, dt)) {
     L.rate_constants(m, T);
     // first step: the size the previous solve of this cell ended with (OpenFOAM's per-cell deltaTChem)
     const double hp = stats[2 * n + c];
@@ -1131,7 +1190,7 @@ __global__ void __launch_bounds__(TG * NCB) k_chem_coop(long n, const int* __res
     qh[s] = 0.0;
     if (i < S) {
       const double Yn = y[s] * Wl[s] / rho;
-      const double rr = T >= Tmin ? (Yn - Yf[(long)i * n + c]) * rho_rr / dt : 0.0;
+      const double rr = T >= Tmin && dt_live(dt_in, dt) ? (Yn - Yf[(long)i * n + c]) * rho_rr / dt : 0.0;
       RR[(long)i * n + c] = rr;
       qh[s] = hc[i] * rr;
     }
@@ -1156,6 +1215,7 @@ unsigned long long fnv(unsigned long long h, const void* p, size_t n) {
 
 }  // namespace
 
+#ifndef DFMI_CHEM_CELLS
 void chem_upload(Ctx& x, int R, const int* idata, const int* irs, const double* dd) {
   Chem& h = x.chem;
   DFMI_CHECK(x.S > 0 && R > 0 && R <= 256, "chemistry: bad reaction count");
@@ -1207,12 +1267,14 @@ void chem_upload(Ctx& x, int R, const int* idata, const int* irs, const double* 
   h.ready = true;
 }
 
+#endif
 namespace {
 // lanes per cell of the cooperative kernel by species count (profiles/chem_coop.json)
 int coop_lanes_for(int S) { return S <= 16 ? 16 : (S <= 32 ? 32 : 64); }
 }  // namespace
 
-void chem_solve(Ctx& x, double dt, const char* rho_field) {
+namespace {
+template <class DT> void chem_solve_t(Ctx& x, DT dt, const char* rho_field) {
   Chem& h = x.chem;
   DFMI_CHECK(h.ready, "chemistry mechanism not set (dfmi_chem_set_mechanism)");
   DFMI_CHECK(x.thermo.S == x.S, "chemistry needs the thermo coefficients (NASA7, W)");
@@ -1283,9 +1345,9 @@ void chem_solve(Ctx& x, double dt, const char* rho_field) {
     KScope _ks(x, "k_chem");
 #define COOP(TG, NCB)                                                                                               \
   do {                                                                                                              \
-    DFMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chem_coop<TG, NCB>),                             \
+    DFMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chem_coop<TG, NCB, DT>),                             \
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds));                           \
-    hipLaunchKernelGGL((k_chem_coop<TG, NCB>), dim3((unsigned)cb), dim3(TG * NCB), clds, x.stream, (long)x.C, perm, m, \
+    hipLaunchKernelGGL((k_chem_coop<TG, NCB, DT>), dim3((unsigned)cb), dim3(TG * NCB), clds, x.stream, (long)x.C, perm, m, \
                        cl, x.S, x.f("T"), x.f("p"), rho_rr, x.f("Y"), dt, h.rtol, h.atol, h.Tmin, h.max_steps,     \
                        x.f("RR"), stats, h.fail.p, tiled, x.thermo.dhc.p, x.f("Qdot"));                            \
   } while (0)
@@ -1298,7 +1360,7 @@ void chem_solve(Ctx& x, double dt, const char* rho_field) {
   }
   if (h.generated) {
     KScope _ks(x, "k_chem");
-#define GEN(G) hipLaunchKernelGGL((k_chem_gen<G>), g, dim3(LANES), 0, x.stream, (long)x.C, perm, x.f("T"), x.f("p"),  \
+#define GEN(G) hipLaunchKernelGGL((k_chem_gen<G, DT>), g, dim3(LANES), 0, x.stream, (long)x.C, perm, x.f("T"), x.f("p"),  \
                                   rho_rr, x.f("Y"), dt, h.rtol, h.atol, h.Tmin, h.max_steps, x.f("RR"), stats, h.fail.p, tiled,   \
                                   x.thermo.dhc.p, x.f("Qdot"))
     if (h.generated == 1) GEN(ChemGen_burke9); else GEN(ChemGen_es80);
@@ -1310,7 +1372,7 @@ void chem_solve(Ctx& x, double dt, const char* rho_field) {
 #define CALL(NS)                                                                                                    \
   do {                                                                                                              \
     KScope _ks(x, "k_chem");                                                                                        \
-    hipLaunchKernelGGL(k_chem<NS>, g, dim3(LANES), lds, x.stream, (long)x.C, perm, m, x.f("T"), x.f("p"), rho_rr,      \
+    hipLaunchKernelGGL((k_chem<NS, DT>), g, dim3(LANES), lds, x.stream, (long)x.C, perm, m, x.f("T"), x.f("p"), rho_rr,      \
                        x.f("Y"), dt, h.rtol, h.atol, h.Tmin, h.max_steps, h.method, x.f("RR"), stats, h.fail.p, tiled,   \
                        x.thermo.dhc.p, x.f("Qdot"));                                                          \
   } while (0)
@@ -1324,6 +1386,15 @@ void chem_solve(Ctx& x, double dt, const char* rho_field) {
   DFMI_HIP(hipGetLastError());
   chem_fail_snapshot(x);
 }
+}  // namespace
+
+// The per-cell-interval instantiations are compiled in a translation unit of their own (chem_cells.hip includes this
+// file with DFMI_CHEM_CELLS defined): with both sets in one unit the generated kinetics' functions have two callers, the
+// inliner decides otherwise, and k_chem_gen<burke9> -- at its register limit -- changes (profiles/tci_resource_usage.md)
+#ifdef DFMI_CHEM_CELLS
+void chem_solve_cells(Ctx& x, const double* dt_cell, const char* rho_field) { chem_solve_t<const double*>(x, dt_cell, rho_field); }
+#else
+void chem_solve(Ctx& x, double dt, const char* rho_field) { chem_solve_t<double>(x, dt, rho_field); }
 
 // The failure count leaves the device behind an event (no stream drain); chem_check reads it at the
 // next host synchronisation point the caller already has (end of the time step's solver polls).
@@ -1348,4 +1419,391 @@ void chem_check(Ctx& x) {
                           "); their RR is not a completed integration");
 }
 
+// ---- turbulence-chemistry interaction: PaSR and EDC (options tci.*; include/dfmi.h) ----------------
+namespace {
+constexpr double TCI_SMALL = 1e-15, TCI_VGREAT = 1e300;
+
+struct TciPar {
+  int model, mixing, chem, version, e1, e2, fuel, ox, co2, h2;
+  double Cmix, C1, C2, Cgamma, Ctau;
+};
+
+// PaSR chemistryScale reactionRate (PaSR.C:326-377): tc = sumW / sumSq * cSum from the forward and reverse rates of
+// progress at Cantera's setState_TPX(T, p, X), X_i = rho Y_i / W_i. One cell per lane, the rate constants in LDS as
+// k_chem keeps them; f and b are the expressions rhs() differences. Sums in reaction order, wf then wr.
+template <int S>
+__global__ void __launch_bounds__(LANES) k_tci_rates(long n, ChemMech m, const double* __restrict__ Tf,
+                                                     const double* __restrict__ pf, const double* __restrict__ rhof,
+                                                     const double* __restrict__ Yf, double* __restrict__ tc) {
+  extern __shared__ double lds[];
+  Lane<S> L;
+  L.lane = threadIdx.x;
+  L.kf = lds;
+  L.k0 = lds + (long)m.R * LANES;
+  L.ikc = lds + 2L * m.R * LANES;
+  L.A = nullptr;
+  const long c = (long)blockIdx.x * LANES + threadIdx.x;
+  if (c >= n) return;   // no block-level synchronisation below
+  const double T = Tf[c], rho = rhof[c];
+  double X[S], C[S];
+  double cSum = 0.0;
+#pragma unroll
+  for (int i = 0; i < S; ++i) {
+    X[i] = rho * Yf[(long)i * n + c] / m.W[i];
+    cSum += X[i];
+  }
+  {   // setState_TPX: mole fractions clipped at 0 and normalised, C_i = x_i p / (R T)
+    double xs = 0.0;
+#pragma unroll
+    for (int i = 0; i < S; ++i) xs += fmax(X[i], 0.0);
+    const double ct = pf[c] / (RU * T);
+#pragma unroll
+    for (int i = 0; i < S; ++i) C[i] = fmax(X[i], 0.0) / xs * ct;
+  }
+  rate_constants<S>(m, L, T);
+  double sumW = 0.0, sumSq = 0.0;
+  for (int r = 0; r < m.R; ++r) {
+    const int* id = m.idata + r * 8;
+    const int* ix = m.irs + r * 6;
+    const double* d = m.dd + (long)r * m.ndd;
+    double k, Mf, Mc;
+    rcoef<S>(m, L, r, T, C, k, Mf, Mc);
+    double f = k, b = id[1] ? k * L.K(L.ikc, r) : 0.0;
+    for (int j = 0; j < 3; ++j) {
+      if (ix[j] >= 0) f *= ipow(sel<S>(C, ix[j]), d[3 + j]);
+      if (ix[3 + j] >= 0) b *= ipow(sel<S>(C, ix[3 + j]), d[6 + j]);
+    }
+    const double fwd = Mf * f, rev = Mf * b;
+    double wf = 0.0, wr = 0.0;
+    for (int j = 0; j < 3; ++j) {
+      if (ix[3 + j] >= 0) wf += d[6 + j] * fwd;
+      if (ix[j] >= 0) wr += d[3 + j] * rev;
+    }
+    sumW += wf; sumW += wr;
+    sumSq += wf * wf; sumSq += wr * wr;
+  }
+  tc[c] = sumSq == 0.0 ? TCI_VGREAT : sumW / sumSq * cSum;
+}
+
+// doubles of LDS one cell of the cooperative rates kernel takes: kf k0 ikc wf wr [R], C bv [S]
+inline size_t tci_coop_cell_doubles(int S, int R) { return 5 * (size_t)R + 2 * (size_t)S; }
+
+// the same for 13..64 species (and under chem.coop = 1): TG lanes per cell, the layout of k_chem_coop without its matrix
+template <int TG, int NCB>
+__global__ void __launch_bounds__(TG * NCB) k_tci_rates_coop(long n, ChemMech m, int S, const double* __restrict__ Tf,
+                                                             const double* __restrict__ pf, const double* __restrict__ rhof,
+                                                             const double* __restrict__ Yf, double* __restrict__ tc) {
+  static_assert(LANES % TG == 0 && (TG * NCB) % LANES == 0, "a cell must not straddle waves");
+  constexpr int RPL = Coop<TG>::RPL;
+  extern __shared__ double lds[];
+  const int R = m.R;
+  Coop<TG> L;
+  L.S = S; L.R = R; L.LD = S | 1; L.l = threadIdx.x % TG;
+  {
+    double* base = lds + (size_t)(threadIdx.x / TG) * (5 * (size_t)R + 2 * (size_t)S);
+    L.A = nullptr;
+    L.kf = base; L.k0 = base + R; L.ikc = base + 2 * R; L.ke = base + 3 * R; L.Mf = base + 4 * R;
+    L.tb = nullptr; L.q = nullptr;
+    base += 5 * R;
+    L.C = base; L.bv = base + S;
+  }
+  const long c = (long)blockIdx.x * NCB + threadIdx.x / TG;
+  if (c >= n) return;   // no workgroup barrier below: a cell is inside one wave
+  const double T = Tf[c], rho = rhof[c];
+  double X[RPL], a[RPL];
+#pragma unroll
+  for (int s = 0; s < RPL; ++s) {
+    const int i = L.row(s);
+    X[s] = i < S ? rho * Yf[(long)i * n + c] / m.W[i] : 0.0;
+    a[s] = fmax(X[s], 0.0);
+  }
+  const double cSum = L.ordered_sum(X);
+  const double xs = L.ordered_sum(a);
+  const double ct = pf[c] / (RU * T);
+#pragma unroll
+  for (int s = 0; s < RPL; ++s) a[s] = a[s] / xs * ct;
+  L.rate_constants(m, T);
+  L.publish(a);
+  L.progress(m, T);
+  if (L.l == 0) {
+    double sumW = 0.0, sumSq = 0.0;
+    for (int r = 0; r < R; ++r) {
+      const double wf = L.ke[r], wr = L.Mf[r];
+      sumW += wf; sumW += wr;
+      sumSq += wf * wf; sumSq += wr * wr;
+    }
+    tc[c] = sumSq == 0.0 ? TCI_VGREAT : sumW / sumSq * cSum;
+  }
+}
+
+__device__ __forceinline__ double tci_ipow(double g, int e) {   // g^e, e in 1..4, as left-to-right products
+  double v = g;
+  for (int i = 1; i < e; ++i) v = v * g;
+  return v;
+}
+
+// The pointwise pass. PaSR (after the solve): tmix, the RR-based tc forms (reactionRate: tc as k_tci_rates left it),
+// kappa, and the consumers' RR_eff = kappa RR, Qdot_eff = kappa Qdot. EDC (before the solve): kappa and tauStar, the
+// v2016 branch with tc the formationRate form of the RR the previous solve left; tauStar not positive and finite is counted.
+// ST > 0: S = ST species held in registers, RR read once; ST = 0: any S, RR read again for the scaling.
+template <int ST>
+__global__ void __launch_bounds__(256) k_tci_kappa(long n, int S_rt, TciPar P, const double* __restrict__ kf,
+                                                   const double* __restrict__ epsf, const double* __restrict__ muf,
+                                                   const double* __restrict__ rhof, const double* __restrict__ Yf,
+                                                   const double* __restrict__ RR, const double* __restrict__ Qdot,
+                                                   double* __restrict__ tcf, double* __restrict__ tmixf,
+                                                   double* __restrict__ tauf, double* __restrict__ kappaf,
+                                                   double* __restrict__ RReff, double* __restrict__ Qeff,
+                                                   int* __restrict__ bad) {
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n) return;
+  const int S = ST ? ST : S_rt;
+  const double k = kf[c], eps = epsf[c], mu = muf[c], rho = rhof[c];
+  double rr[ST ? ST : 1];
+  if (ST) {
+#pragma unroll
+    for (int i = 0; i < (ST ? ST : 1); ++i) rr[i] = RR[(long)i * n + c];
+  }
+  auto rr_at = [&](int i) -> double {
+    if (ST) {
+      double o = 0.0;
+#pragma unroll
+      for (int j = 0; j < (ST ? ST : 1); ++j) o = (j == i) ? rr[j] : o;
+      return o;
+    }
+    return RR[(long)i * n + c];
+  };
+  // laminar::tc() (laminar.C:75-102), the formationRate form
+  auto formation = [&]() -> double {
+    double t = 0.0;
+    if (ST) {
+#pragma unroll
+      for (int i = 0; i < (ST ? ST : 1); ++i) {
+        const double a = fabs(rr[i]);
+        t = fmax(t, a > TCI_SMALL ? Yf[(long)i * n + c] / a : 0.0);
+      }
+    } else {
+      for (int i = 0; i < S; ++i) {
+        const double a = fabs(RR[(long)i * n + c]);
+        t = fmax(t, a > TCI_SMALL ? Yf[(long)i * n + c] / a : 0.0);
+      }
+    }
+    return t;
+  };
+  if (P.model == 1) {
+    const double e = eps + TCI_SMALL;
+    double tmix;
+    if (P.mixing == 1) tmix = P.Cmix * k / e;
+    else if (P.mixing == 2) tmix = sqrt(fabs(mu / rho / e));
+    else tmix = sqrt(fabs(k / e) * sqrt(fabs(mu / rho / e)));
+    double tc;
+    if (P.chem == 1) {
+      const double t0 = tcf[c];
+      bool first = true;
+      tc = 0.0;
+      auto take = [&](double t) { tc = first ? t : fmax(tc, t); first = false; };
+      if (P.ox >= 0) { const double r = rr_at(P.ox), y = Yf[(long)P.ox * n + c]; take(r < 0.0 && y > 1e-10 ? -rho * y / r : t0); }
+      if (P.fuel >= 0) { const double r = rr_at(P.fuel), y = Yf[(long)P.fuel * n + c]; take(r < 0.0 && y > 1e-10 ? -rho * y / r : t0); }
+      if (P.co2 >= 0) { const double r = rr_at(P.co2), y = Yf[(long)P.co2 * n + c]; take(r > 0.0 && y > 1e-10 ? rho * y / r : t0); }
+      if (P.h2 >= 0) { const double r = rr_at(P.h2), y = Yf[(long)P.h2 * n + c]; take(r < 0.0 && y > 1e-10 ? -rho * y / r : t0); }
+    } else if (P.chem == 2) tc = formation();
+    else tc = tcf[c];
+    const double kappa = (tmix > TCI_SMALL && tc > TCI_SMALL) ? tc / (tc + tmix) : 1.0;
+    tcf[c] = tc;
+    tmixf[c] = tmix;
+    kappaf[c] = kappa;
+    if (ST) {
+#pragma unroll
+      for (int i = 0; i < (ST ? ST : 1); ++i) RReff[(long)i * n + c] = kappa * rr[i];
+    } else {
+      for (int i = 0; i < S; ++i) RReff[(long)i * n + c] = kappa * RR[(long)i * n + c];
+    }
+    Qeff[c] = kappa * Qdot[c];
+    return;
+  }
+  // EDC (EDC.C:83-171)
+  const double nu = mu / (rho + TCI_SMALL);
+  const double tk = sqrt(nu / (eps + TCI_SMALL));
+  const double g4 = sqrt(sqrt(nu * eps / (k * k + TCI_SMALL)));
+  double gammaL, tauStar;
+  if (P.version == 2016) {
+    const double tc = formation();
+    tcf[c] = tc;
+    const double Da = fmax(fmin(tk / tc, 10.0), 1e-10);
+    const double ReT = k * k / (nu * eps + TCI_SMALL);
+    const double CtauI = fmin(P.C1 / (Da * sqrt(ReT + 1.0)), 2.1377);
+    const double CgammaI = fmax(fmin(P.C2 * sqrt(Da * (ReT + 1.0)), 5.0), 0.4082);
+    gammaL = CgammaI * g4;
+    tauStar = CtauI * tk;
+  } else {
+    gammaL = P.Cgamma * g4;
+    tauStar = P.Ctau * tk;
+  }
+  const double kappa = gammaL >= 1.0 ? 1.0 : fmax(fmin(tci_ipow(gammaL, P.e1) / (1.0 - tci_ipow(gammaL, P.e2)), 1.0), 0.0);
+  kappaf[c] = kappa;
+  tauf[c] = tauStar;
+  if (!(tauStar > 0.0 && tauStar <= 1.79769313486231570e308)) atomicAdd(bad, 1);   // integer count
+}
+
+// EDC's consumers after the solve: RR_eff = kappa RR, Qdot_eff = kappa Qdot
+__global__ void __launch_bounds__(256) k_tci_scale(long n, int S, const double* __restrict__ kappaf,
+                                                   const double* __restrict__ RR, const double* __restrict__ Qdot,
+                                                   double* __restrict__ RReff, double* __restrict__ Qeff) {
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n) return;
+  const double kappa = kappaf[c];
+  for (int i = 0; i < S; ++i) RReff[(long)i * n + c] = kappa * RR[(long)i * n + c];
+  Qeff[c] = kappa * Qdot[c];
+}
+
+__global__ void __launch_bounds__(256) k_tci_fill(long n, double v, double* __restrict__ a) {
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < n) a[c] = v;
+}
+
+TciPar tci_par(Ctx& x) {
+  TciPar P;
+  P.model = x.tci.model;
+  P.mixing = (int)x.opt("tci.mixing");
+  P.chem = (int)x.opt("tci.chemistry");
+  P.version = (int)x.opt("tci.version");
+  P.e1 = (int)x.opt("tci.exp1");
+  P.e2 = (int)x.opt("tci.exp2");
+  const int d1 = P.version == 1981 ? 3 : 2, d2 = (P.version == 1981 || P.version == 1996) ? 3 : 2;
+  if (P.e1 == 0) P.e1 = d1;
+  if (P.e2 == 0) P.e2 = d2;
+  P.fuel = (int)x.opt("tci.fuel"); P.ox = (int)x.opt("tci.oxidizer"); P.co2 = (int)x.opt("tci.CO2"); P.h2 = (int)x.opt("tci.H2");
+  P.Cmix = x.opt("tci.Cmix"); P.C1 = x.opt("tci.C1"); P.C2 = x.opt("tci.C2"); P.Cgamma = x.opt("tci.Cgamma"); P.Ctau = x.opt("tci.Ctau");
+  return P;
+}
+
+void tci_rates(Ctx& x) {
+  Chem& h = x.chem;
+  ChemMech m{h.R, h.ndd, h.idata.p, h.irs.p, h.dd.p, x.thermo.dnasa.p, x.thermo.dW.p};
+  const bool coop = x.S > 12 || x.on("chem.coop");
+  KScope _ks(x, "k_tci_rates");
+  if (coop) {
+    const int tg = coop_lanes_for(x.S);
+    const int ncb = LANES / tg;
+    const size_t clds = tci_coop_cell_doubles(x.S, h.R) * sizeof(double) * ncb;
+    DFMI_CHECK(clds <= 64 * 1024, "tci reactionRate: mechanism too large for the LDS layout");
+    const dim3 g((unsigned)blocks_for((long)x.C, ncb));
+#define COOP(TG, NCB)                                                                                              \
+  hipLaunchKernelGGL((k_tci_rates_coop<TG, NCB>), g, dim3(TG * NCB), clds, x.stream, (long)x.C, m, x.S, x.f("T"),   \
+                     x.f("p"), x.f("rho"), x.f("Y"), x.f("tci_tc"))
+    if (tg == 16) COOP(16, 4); else if (tg == 32) COOP(32, 2); else COOP(64, 1);
+#undef COOP
+    DFMI_HIP(hipGetLastError());
+    return;
+  }
+  const size_t lds = (size_t)3 * h.R * LANES * sizeof(double);
+  DFMI_CHECK(lds <= 64 * 1024, "tci reactionRate: mechanism too large for the LDS layout");
+  const dim3 g((unsigned)blocks_for((long)x.C, LANES));
+#define CALL(NS)                                                                                                   \
+  hipLaunchKernelGGL(k_tci_rates<NS>, g, dim3(LANES), lds, x.stream, (long)x.C, m, x.f("T"), x.f("p"), x.f("rho"), \
+                     x.f("Y"), x.f("tci_tc"))
+  switch (x.S) {
+    case 4: CALL(4); break; case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break;
+    case 8: CALL(8); break; case 9: CALL(9); break; case 10: CALL(10); break; case 11: CALL(11); break;
+    case 12: CALL(12); break;
+    default: throw Error("tci reactionRate: species count " + std::to_string(x.S) + " not instantiated");
+  }
+#undef CALL
+  DFMI_HIP(hipGetLastError());
+}
+
+void tci_kappa(Ctx& x, const TciPar& P) {
+  KScope _ks(x, "k_tci_kappa");
+  const dim3 g((unsigned)blocks_for((long)x.C, 256));
+#define CALL(NS)                                                                                                       \
+  hipLaunchKernelGGL(k_tci_kappa<NS>, g, dim3(256), 0, x.stream, (long)x.C, x.S, P, x.f("k"), x.f("epsilon"), x.f("mu"), \
+                     x.f("rho"), x.f("Y"), x.f("RR"), x.f("Qdot"), x.f("tci_tc"), x.f("tci_tmix"), x.f("tci_tauStar"),  \
+                     x.f("tci_kappa"), x.f("RR_eff"), x.f("Qdot_eff"), x.tci.bad.p)
+  switch (x.S) {
+    case 4: CALL(4); break; case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break;
+    case 8: CALL(8); break; case 9: CALL(9); break; case 10: CALL(10); break; case 11: CALL(11); break;
+    case 12: CALL(12); break;
+    default: CALL(0); break;
+  }
+#undef CALL
+  DFMI_HIP(hipGetLastError());
+}
+}  // namespace
+
+void ensure_tci_fields(Ctx& x) {
+  if (x.fields.count("tci_kappa")) return;
+  DFMI_CHECK(x.have_sizes, "call dfmi_set_constant_values first");
+  auto mk = [&](const char* name, long n, int ncomp) {
+    Field& f = x.fields[name];
+    f.n = n; f.ncomp = ncomp; f.boundary = false; f.face = false;
+    f.buf.alloc((size_t)n * ncomp);
+    f.buf.zero(x.stream);
+  };
+  for (auto n : {"tci_kappa", "tci_tmix", "tci_tauStar", "tci_tc", "Qdot_eff"}) mk(n, x.C, 1);
+  mk("RR_eff", x.C, x.S);
+  x.tci.bad.alloc(1);
+  DFMI_HIP(hipMemsetAsync(x.tci.bad.p, 0, sizeof(int), x.stream));
+  tci_reset_tc(x);
+}
+
+// tci_tc starts at 0.1 (PaSR.C:77: tc_ is constructed with that value) and persists from call to call
+void tci_reset_tc(Ctx& x) {
+  if (!x.fields.count("tci_tc")) return;
+  hipLaunchKernelGGL(k_tci_fill, dim3((unsigned)blocks_for((long)x.C, 256)), dim3(256), 0, x.stream, (long)x.C, 0.1, x.f("tci_tc"));
+}
+
+namespace {
+TciPar tci_validate(Ctx& x) {
+  DFMI_CHECK(x.ras.model == 1, "tci.model != 0 needs ras.model = 1 (k and epsilon exist only there)");
+  DFMI_CHECK(!x.les.model, "tci.model != 0 and les.model != 0 exclude each other");
+  DFMI_CHECK(x.chem.mode != 2, "tci.model != 0 is not available with the DNN surrogate (chemistry mode 2)");
+  DFMI_CHECK(x.chem.mode == 1, "tci.model != 0 needs chemistry mode 1 (stiff integration; dfmi_chem_set_options)");
+  for (int i = 0; i < 2; ++i)
+    DFMI_CHECK(x.ras.have[i], std::string("tci: the field '") + (i ? "epsilon" : "k") + "' is not set (dfmi_set_field)");
+  const TciPar P = tci_par(x);
+  DFMI_CHECK(!(P.model == 1 && P.chem == 1 && P.fuel < 0),
+             "tci.chemistry = 1 (globalConvertion) needs tci.fuel >= 0 (PaSR.C:259-264: the fuel species is not set)");
+  for (int i : {P.fuel, P.ox, P.co2, P.h2}) DFMI_CHECK(i < x.S, "tci: a species index is outside the mechanism's species");
+  DFMI_CHECK(x.chem.ready || !(P.model == 1 && P.chem == 3), "chemistry mechanism not set (dfmi_chem_set_mechanism)");
+  ensure_tci_fields(x);
+  return P;
+}
+void tci_scale(Ctx& x) {
+  KScope _ks(x, "k_tci_scale");
+  hipLaunchKernelGGL(k_tci_scale, dim3((unsigned)blocks_for((long)x.C, 256)), dim3(256), 0, x.stream, (long)x.C, x.S,
+                     x.f("tci_kappa"), x.f("RR"), x.f("Qdot"), x.f("RR_eff"), x.f("Qdot_eff"));
+  DFMI_HIP(hipGetLastError());
+}
+}  // namespace
+
+void combustion_correct(Ctx& x, double dt, const char* rho_field) {
+  if (!x.tci.model) { chem_solve(x, dt, rho_field); return; }   // laminar: combustion->correct() is the solve
+  const TciPar P = tci_validate(x);
+  if (P.model == 1) {
+    chem_solve(x, dt, rho_field);   // laminar::correct()
+    if (P.chem == 3) tci_rates(x);
+    tci_kappa(x, P);
+    return;
+  }
+  DFMI_HIP(hipMemsetAsync(x.tci.bad.p, 0, sizeof(int), x.stream));
+  tci_kappa(x, P);
+  chem_solve_cells(x, x.f("tci_tauStar"), rho_field);   // chemistryPtr_->solve(tauStar)
+  tci_scale(x);
+}
+
+// dfmi_assemble("tci"): the closure's pointwise passes from the fields as they stand, RR and Qdot included -- no solve
+void combustion_pointwise(Ctx& x) {
+  DFMI_CHECK(x.tci.model, "dfmi_assemble: 'tci' needs tci.model != 0");
+  const TciPar P = tci_validate(x);
+  if (P.model == 1) {
+    if (P.chem == 3) tci_rates(x);
+    tci_kappa(x, P);
+    return;
+  }
+  DFMI_HIP(hipMemsetAsync(x.tci.bad.p, 0, sizeof(int), x.stream));
+  tci_kappa(x, P);
+  tci_scale(x);
+}
+
+#endif  // DFMI_CHEM_CELLS
 }  // namespace dfmi

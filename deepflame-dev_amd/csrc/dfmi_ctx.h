@@ -290,6 +290,22 @@ inline const OptDef* option_defs(int& n) {
     {"ras.epsilonMin", 1e-15},        // bound(epsilon, epsilonMin)
     {"ras.Prt", 1.0},                 // alphaEff = alpha + mut / Prt (RAS mode)
     {"ras.Sct", 1.0},                 // DEff_i = rhoD_i + mut / Sct (RAS mode)
+    {"tci.model", 0},                 // combustion->correct(): 0 none (laminar), 1 PaSR, 2 EDC (include/dfmi.h)
+    {"tci.mixing", 1},                // PaSR mixingScale: 1 globalScale, 2 kolmogorovScale, 3 geometriMeanScale
+    {"tci.chemistry", 1},             // PaSR chemistryScale: 1 globalConvertion, 2 formationRate, 3 reactionRate
+    {"tci.Cmix", 0.1},                // globalScale: tmix = Cmix k / epsilon
+    {"tci.fuel", -1},                 // globalConvertion species indices; -1: not considered
+    {"tci.oxidizer", -1},
+    {"tci.CO2", -1},
+    {"tci.H2", -1},
+    {"tci.version", 2005},            // EDC: 1981, 1996, 2005, 2016
+    {"tci.C1", 0.05774},              // EDC v2016
+    {"tci.C2", 0.5},
+    {"tci.Cgamma", 2.1377},           // EDC
+    {"tci.Ctau", 0.4083},
+    {"tci.exp1", 0},                  // EDC exponents: 0 the version's own, otherwise 1..4
+    {"tci.exp2", 0},
+    {"tci.bad_tauStar", 0},           // get only: cells of the last EDC correct whose tauStar was not positive and finite
     {"p.n_nonorth", 0},               // nNonOrthogonalCorrectors (system/fvSolution PIMPLE): extra passes of the pEqn's
                                       // non-orthogonal corrector loop (pEqn.H:51-62)
   };
@@ -456,6 +472,10 @@ struct Ctx {
   struct Ras { int model = 0; bool valid = false; bool have[4] = {false, false, false, false}; } ras;
   // the one flag everything downstream of an eddy viscosity reads: either model sets it (the effective fields, the
   // dropped YEqn / EEqn terms, the LES instantiations of the assemblies)
+  // combustion closure (options tci.*, chem.hip tci_*): the model in force; bad: the device count of EDC cells without a usable tauStar
+  struct Tci { int model = 0; DevBuf<int> bad; } tci;
+  // the chemistry source the YEqn assemblies read: the closure's kappa RR, or the chemistry's own RR
+  double* rr_src() { return f(tci.model ? "RR_eff" : "RR"); }
   bool turbulent() const { return les.model != 0 || ras.model != 0; }
   // what the three assemblies read as mu / alpha: the thermo's fields, or in turbulent mode muEff / alphaEff (les_effective)
   double* visc(bool boundary) { return f(std::string(boundary ? "boundary_" : "") + (turbulent() ? "muEff" : "mu")); }
@@ -633,6 +653,14 @@ void chem_upload(Ctx& x, int R, const int* idata, const int* irs, const double* 
 // rho_field: the thermo density RR is scaled by (dfChemistryModel.C:771, problem.rhoi = rho_[celli]);
 // inside dfmi_time_step that is rho_old (thermo.rho() before this step's rhoEqn), standalone "rho"
 void chem_solve(Ctx& x, double dt, const char* rho_field);
+// the same solve over a per-cell interval dt_cell[c] (EDC's chemistryPtr_->solve(tauStar)); a cell whose interval is not
+// positive and finite gets RR = 0
+void chem_solve_cells(Ctx& x, const double* dt_cell, const char* rho_field);
+// combustion->correct() (PaSR.C:205-396, EDC.C:83-171; include/dfmi.h): tci.model = 0 is chem_solve(dt) alone
+void combustion_correct(Ctx& x, double dt, const char* rho_field);
+void combustion_pointwise(Ctx& x);   // dfmi_assemble("tci"): kappa, the time scales and the scaled source, no solve
+void ensure_tci_fields(Ctx& x);
+void tci_reset_tc(Ctx& x);
 void chem_fail_snapshot(Ctx& x);
 // throws when the last solve left cells at the step limit (waits on the snapshot event only)
 void chem_check(Ctx& x);

@@ -2976,11 +2976,11 @@ void y_assemble(Ctx& x) {
   Matrix& A = x.mY;
   MeshView m = x.view();
 #define CALL(NS) LAUNCH_SWL(k_y_assemble, NS, x.C, m, x.st("Y"), x.inert, x.f("Y"), x.f("boundary_Y"), x.f("rhoD"),   \
-                        x.f("boundary_rhoD"), x.f("RR"), x.f("rho"), x.f("rho_old"), x.f("phi"), x.f("boundary_phi"), \
+                        x.f("boundary_rhoD"), x.rr_src(), x.f("rho"), x.f("rho_old"), x.f("phi"), x.f("boundary_phi"), \
                         x.f("phiUc"), x.f("boundary_phiUc"), A.lower.p, A.upper.p, A.diag.p, A.source.p, A.ic.p, A.bc.p, mixbc(x, "Y"), x.sch_w(0), x.sch_w(1))
   DFMI_SWITCH_S(x.S, CALL,
                 LAUNCH_SWGL(k_y_assemble_gen, YCH, x.C, m, x.S, x.st("Y"), x.inert, x.f("Y"), x.f("boundary_Y"), x.f("rhoD"),
-                       x.f("boundary_rhoD"), x.f("RR"), x.f("rho"), x.f("rho_old"), x.f("phi"), x.f("boundary_phi"),
+                       x.f("boundary_rhoD"), x.rr_src(), x.f("rho"), x.f("rho_old"), x.f("phi"), x.f("boundary_phi"),
                        x.f("phiUc"), x.f("boundary_phiUc"), A.lower.p, A.upper.p, A.diag.p, A.source.p, A.ic.p, A.bc.p, mixbc(x, "Y"), x.sch_w(0), x.sch_w(1)))
 #undef CALL
   if (x.lap == LAP_CORRECTED) nonorth_y(x, A.source.p, nullptr, 0);
@@ -2991,7 +2991,7 @@ void y_assemble_ell(Ctx& x, int W, long Ce, double* val, double* dS, double* rhs
   // (the z-marching tile form measured slower than this cell-parallel kernel, 961 vs 622 us, and is removed)
 #define CALL(NS)                                                                                                     \
   LAUNCH_SWL(k_y_assemble_ell, NS, x.C, m, x.st("Y"), x.inert, x.f("Y"), x.f("boundary_Y"), x.f("rhoD"),              \
-            x.f("boundary_rhoD"), x.f("RR"), x.f("rho"), x.f("rho_old"), x.f("phi"),                                 \
+            x.f("boundary_rhoD"), x.rr_src(), x.f("rho"), x.f("rho_old"), x.f("phi"),                                 \
             x.f("boundary_phi"), x.f("phiUc"), x.f("boundary_phiUc"), W, Ce, val, dS, rhs, mixbc(x, "Y"), x.sch_w(0), x.sch_w(1))
   // chunked kernel: 8 species per chunk, species ranges of YASM_LCH per launch (assembly 5.98 -> 5.86 ms per step
   // on 2M x 53 species with 8)
@@ -3000,7 +3000,7 @@ void y_assemble_ell(Ctx& x, int W, long Ce, double* val, double* dS, double* rhs
     constexpr int lch = YASM_LCH / CH * CH;                                                                          \
     for (int s_lo = 0; s_lo < x.S; s_lo += lch)                                                                      \
       LAUNCH_SWGL(k_y_assemble_ell_gen, CH, x.C, m, s_lo, std::min(x.S, s_lo + lch), x.st("Y"), x.inert, x.f("Y"),    \
-                 x.f("boundary_Y"), x.f("rhoD"), x.f("boundary_rhoD"), x.f("RR"), x.f("rho"), x.f("rho_old"), x.f("phi"), \
+                 x.f("boundary_Y"), x.f("rhoD"), x.f("boundary_rhoD"), x.rr_src(), x.f("rho"), x.f("rho_old"), x.f("phi"), \
                  x.f("boundary_phi"), x.f("phiUc"), x.f("boundary_phiUc"), W, Ce, val, dS, rhs, mixbc(x, "Y"),       \
                  x.sch_w(0), x.sch_w(1));                                                                            \
   } while (0)

@@ -84,6 +84,7 @@ SIGNATURES = {
     "dfmi_chem_set_mechanism": [_P, C.c_int, _IP, _IP, _DP],
     "dfmi_chem_set_options": [_P, C.c_int, C.c_double, C.c_double, C.c_double],
     "dfmi_chem_solve": [_P, C.c_double],
+    "dfmi_combustion_correct": [_P, C.c_double],
     "dfmi_chem_set_max_steps": [_P, C.c_int],
     "dfmi_zero_d_step": [_P, C.c_double, C.c_int],
     "dfmi_renumber_cells": [C.c_int, _DP, C.c_int, _IP, _IP, C.c_char_p, _IP],
@@ -344,6 +345,11 @@ class Context:
 
     def chem_solve(self, dt):
         self._call("dfmi_chem_solve", self.h, float(dt))
+
+    def combustion_correct(self, dt):
+        """combustion->correct() (include/dfmi.h dfmi_combustion_correct; options tci.*): the chemistry solve and, with
+        a PaSR or EDC closure in force, kappa and the scaled source RR_eff / Qdot_eff. tci.model = 0: chem_solve(dt)."""
+        self._call("dfmi_combustion_correct", self.h, float(dt))
 
     def zero_d_step(self, dt, n_steps=1):
         """df0DFoam time steps on every cell (include/dfmi.h dfmi_zero_d_step)"""

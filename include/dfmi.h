@@ -174,7 +174,8 @@ int dfmi_thermo_load(dfmi_ctx* ctx, const char* thermo_coeff_file);
  *        boundary_{U,p,Y,K}_ref (inletOutlet inletValue), boundary_p_vf (waveTransmissive valueFraction),
  *        boundary_p_gamma, chem_stats [3][C]. count = values per component.
  *        LES: delta (cells; positive), nut (cells; get only), boundary_nut (set: the fixedValue / calculated slots).
- *        RAS: k epsilon (cells), boundary_{k,epsilon}, boundary_{k,epsilon}_ref; get only: G divU k_prebound epsilon_prebound. */
+ *        RAS: k epsilon (cells), boundary_{k,epsilon}, boundary_{k,epsilon}_ref; get only: G divU k_prebound epsilon_prebound.
+ *        Combustion closure: tci_tc (cells); get only: tci_kappa tci_tmix tci_tauStar Qdot_eff (cells), RR_eff (species). */
 int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long count, int layout);
 int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, int layout);
 
@@ -297,8 +298,11 @@ int dfmi_hbm_copy_peak(dfmi_ctx* ctx, double gib, int reps, double* gbs);
 int dfmi_correct_boundary(dfmi_ctx* ctx, const char* field);
 
 /* ---- matrix inspection (the reference DEBUG_CHECK_LDU / compareResult path, dfYEqn.cu:566-572) */
-/* eqn in {"rho","U","Y","E","p","HbyA","Y_ell","Y_ell_ref","epsilon","k"}: run that equation's assembly only (no solve); under
- * the laplacian scheme "corrected" the sources include the explicit term ("p": that of the corrector loop's first pass) */
+/* eqn in {"rho","U","Y","E","p","HbyA","Y_ell","Y_ell_ref","epsilon","k","tci"}: run that equation's assembly only (no solve); under
+ * the laplacian scheme "corrected" the sources include the explicit term ("p": that of the corrector loop's first pass).
+ * "tci" (tci.model != 0): the closure's pointwise passes of dfmi_combustion_correct from the fields as they stand, RR and Qdot
+ * included, without the chemistry solve -- tci_tmix, tci_tc, tci_kappa (PaSR) or tci_kappa, tci_tauStar (EDC), then RR_eff
+ * and Qdot_eff */
 int dfmi_assemble(dfmi_ctx* ctx, const char* eqn);
 /* part in {"lower","upper","diag","source","source_solve","internal_coeffs","boundary_coeffs"} */
 int dfmi_get_matrix(dfmi_ctx* ctx, const char* eqn, const char* part, double* host, long count);
@@ -323,6 +327,8 @@ int dfmi_set_preconditioner(dfmi_ctx* ctx, const char* eqn, const char* name);
  * species_generic, yprep_brick), "chem.*" (method 0 ROS3 | 1 extrapolation, generated, binning),
  * "les.*" (model, Ck, Ce, Cw, Prt, Sct: dfmi_turbulence_correct above),
  * "ras.*" (model, Cmu, C1, C2, C3, sigmak, sigmaEps, kMin, epsilonMin, Prt, Sct: the same call's RAS block),
+ * "tci.*" (model, mixing, chemistry, Cmix, fuel, oxidizer, CO2, H2, version, C1, C2, Cgamma, Ctau, exp1, exp2:
+ * dfmi_combustion_correct below),
  * "dnn.tuned_gemm", "step.courant" (1: dfmi_time_step queues the Courant-number kernel behind its last
  * kernel and posts the result to pinned memory for dfmi_courant_no; 0, the default: nothing added); keys and
  * defaults in INTEGRATION.md. Solver-structure keys must be set before the first solve; unknown keys fail. */
@@ -378,6 +384,60 @@ int dfmi_chem_set_options(dfmi_ctx* ctx, int mode, double rtol, double atol, dou
  * the step size the integration ended with (the next solve's first step). Returns non-zero when any
  * cell hit the step limit (its RR is then not a completed integration). */
 int dfmi_chem_solve(dfmi_ctx* ctx, double dt);
+/* ---- turbulence-chemistry interaction: combustion->correct() (YEqn.H:76) with combustionModel PaSR or EDC
+ * (src/dfCombustionModels/PaSR/PaSR.C:205-396, EDC/EDC.C:83-171; the reference computes both on the host through Cantera and
+ * has neither on its GPU path). The statement below is the definition; SMALL = small = 1e-15, vGreat = 1e300.
+ * Options (dfmi_set_option; an unknown tci.* key is refused by name; coefficients positive and finite):
+ *   tci.model      0 none (default) | 1 PaSR | 2 EDC
+ *   tci.mixing     1 globalScale | 2 kolmogorovScale | 3 geometriMeanScale       (PaSR; dynamicScale is refused by name)
+ *   tci.chemistry  1 globalConvertion | 2 formationRate | 3 reactionRate          (PaSR)
+ *   tci.Cmix 0.1
+ *   tci.fuel, tci.oxidizer, tci.CO2, tci.H2     species indices, -1 = not considered (default -1)
+ *   tci.version    1981 | 1996 | 2005 (default) | 2016                            (EDC)
+ *   tci.C1 0.05774, tci.C2 0.5, tci.Cgamma 2.1377, tci.Ctau 0.4083
+ *   tci.exp1, tci.exp2   0 = the version's own (3,3 / 2,3 / 2,2 / 2,2); otherwise an integer 1..4; a power g^e is the
+ *                        product ((g g) g) g taken left to right, never pow
+ *   tci.bad_tauStar      get only: cells of the last EDC call whose tauStar was not a positive finite number
+ * tci.model != 0 needs ras.model = 1 (k and epsilon exist only there) and chemistry mode 1; together with les.model != 0 or
+ * with chemistry mode 2 (DNN) it is refused. tci.chemistry = 1 without tci.fuel >= 0 is an error naming the key
+ * (PaSR.C:259-264). The reference looks CO2 and H2 up unconditionally and dies on a mechanism without them; here an index
+ * of -1 leaves that species out of the maximum.
+ * Inputs per cell, all as they stand when the call runs: k, epsilon, mu, rho, T, p, Y, RR. Inside dfmi_time_step rho is the
+ * field after the rhoEqn (the rho combustionModel::rho() sees at YEqn.H:76), mu the thermo's, k and epsilon the previous
+ * step's. RR is scaled by the density the solve is scaled by (dfmi_chem_solve).
+ * PaSR: first laminar::correct(), the solve over dt. Then with e = epsilon + SMALL
+ *   tmix  1: Cmix k / e     2: sqrt(|mu / rho / e|)     3: sqrt(|k / e| sqrt(|mu / rho / e|))
+ *   tc    1 globalConvertion (:284-317), t0 = the cell's tci_tc before the call (the field starts at 0.1 and persists):
+ *            t_ox  = (RR_ox  < 0 && Y_ox  > 1e-10) ? -rho Y_ox  / RR_ox  : t0      t_fuel likewise (RR < 0)
+ *            t_CO2 = (RR_CO2 > 0 && Y_CO2 > 1e-10) ?  rho Y_CO2 / RR_CO2 : t0      t_H2 as the fuel (RR < 0)
+ *            tc = max(max(max(t_ox, t_fuel), t_CO2), t_H2), a species with index -1 left out
+ *         2 formationRate (laminar.C:75-102): tc = max_i (|RR_i| > small ? Y_i / |RR_i| : 0), from 0, in species order
+ *         3 reactionRate (:326-377): cSum = sum_i X_i, X_i = rho Y_i / W_i. The gas state is Cantera's setState_TPX(T, p, X):
+ *            x_i = max(X_i, 0) / sum_j max(X_j, 0), C_i = x_i (p / (R T)). fwd_r / rev_r are getFwdRatesOfProgress /
+ *            getRevRatesOfProgress (third-body and fall-off factors included, rev_r = 0 for an irreversible reaction),
+ *            wf_r = sum_products nu_p fwd_r, wr_r = sum_reactants nu_r rev_r, sumW = sum_r (wf_r + wr_r) and
+ *            sumSq = sum_r (wf_r^2 + wr_r^2), each accumulated as wf then wr per reaction in reaction order;
+ *            tc = sumSq == 0 ? vGreat : sumW / sumSq * cSum
+ *   kappa = (tmix > SMALL && tc > SMALL) ? tc / (tc + tmix) : 1
+ * EDC: first kappa and tauStar from the fields as they stand (tc in v2016: the formationRate form of the RR the previous
+ * solve left), then chemistryPtr_->solve(tauStar): every cell is integrated over its own interval,
+ * RR_i = (Y_i(tauStar) - Y_i) rho / tauStar (dfChemistryModel.C:770). With nu = mu / (rho + small), pow025(x) = sqrt(sqrt(x))
+ *   v1981/1996/2005: gammaL = Cgamma pow025(nu eps / (k^2 + small));  tauStar = Ctau sqrt(nu / (eps + small))
+ *   v2016:           Da = max(min(sqrt(nu / (eps + small)) / tc, 10), 1e-10);  ReT = k^2 / (nu eps + small)
+ *                    CtauI = min(C1 / (Da sqrt(ReT + 1)), 2.1377);  CgammaI = max(min(C2 sqrt(Da (ReT + 1)), 5), 0.4082)
+ *                    gammaL = CgammaI pow025(nu eps / (k^2 + small));  tauStar = CtauI sqrt(nu / (eps + small))
+ *   kappa = gammaL >= 1 ? 1 : max(min(gammaL^exp1 / (1 - gammaL^exp2), 1), 0)
+ * A cell whose tauStar is not a positive finite number gets RR = 0, kappa as computed and a count in tci.bad_tauStar (the
+ * reference divides by zero there). A cell below T_min keeps its rule: RR = 0.
+ * Consumers (PaSR.C:401-404,423-430, EDC.C:176-191): the YEqn source is kappa RR_i and the heat release kappa Qdot; the EEqn
+ * is untouched (absolute enthalpy, no Qdot term). Fields: tci_kappa, tci_tmix, tci_tauStar [C] (get), tci_tc [C] (get and
+ * set; reset to 0.1 when tci.model or tci.chemistry changes), RR_eff [S][C] and Qdot_eff [C] (get). RR and Qdot stay the
+ * chemistry's own unscaled values; with tci.model != 0 the YEqn assemblies (dfmi_Y_process, dfmi_assemble("Y" / "Y_ell"),
+ * dfmi_time_step) read RR_eff where they read RR.
+ * With tci.model = 0 this call is dfmi_chem_solve(dt) and nothing else. dfmi_time_step and dfmi_Y_process call it where they
+ * call the chemistry. Returns non-zero when a cell hit the step limit, as the solve does. The CPU-A baseline keeps the keys
+ * and refuses tci.model != 0 by name. */
+int dfmi_combustion_correct(dfmi_ctx* ctx, double dt);
 /* n_steps df0DFoam time steps (applications/solvers/df0DFoam/df0DFoam.C:99-113, YEqn.H, EEqn.H;
  * zeroDReactor constantProperty pressure): per step chemistry.solve(dt) on every cell, YEqn
  * ddt(rho, Yi) == RR_i (Yi.max(0), inert = 1 - sum), he held, correctThermo (T from he), rho = p psi.
