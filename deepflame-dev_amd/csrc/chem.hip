@@ -1327,10 +1327,8 @@ template <class DT> void chem_solve_t(Ctx& x, DT dt, const char* rho_field) {
     int tg = (int)x.opt("chem.coop_lanes");
     DFMI_CHECK(tg == 0 || tg == 16 || tg == 32 || tg == 64, "chem.coop_lanes must be 0 (by species count), 16, 32 or 64");
     const size_t cell = coop_cell_doubles(x.S, h.R) * sizeof(double);
-    if (tg == 0) {
-      tg = coop_lanes_for(x.S);
-      while (tg < LANES && cell * (LANES / tg) > 160 * 1024) tg *= 2;   // fewer cells per workgroup until they fit
-    }
+    // by species count: with R <= 256 that asks for at most 67 KB (S = 16, 4 cells) and 47 KB (S = 32, 2 cells; S = 64)
+    if (tg == 0) tg = coop_lanes_for(x.S);
     const int ncb = LANES / tg;   // one wave per workgroup
     const size_t clds = cell * ncb;
     DFMI_CHECK(clds <= 160 * 1024, "chemistry: " + std::to_string(x.S) + " species / " + std::to_string(h.R) +

@@ -13,7 +13,8 @@
   zerod   zeroD_drm19.json: a constant-pressure df0DFoam trajectory (oracle.zero_d_trajectory, as
           make_zero_d_fixture.py) of stoichiometric CH4/air, dt = 1e-6, from --T0 over --steps steps.
 
-The oracle costs seconds per cell, so the states are spread over --jobs processes."""
+The oracle costs seconds per cell, so the states are spread over --jobs processes. make_chem_sweep_fixtures.py makes the
+states of the species-count sweep the same way."""
 import argparse
 import json
 import multiprocessing
