@@ -1166,6 +1166,14 @@ int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* pt) {
     Ctx& x = ctx->x;
     CHECK(x.have_bgeom, "call dfmi_init_constant_fields_boundary first");
     const std::string f(field);
+    // the HIP library's k-epsilon wall functions and turbulent inlets (codes 13-16): refused by name whatever the field
+    // (k and epsilon are not fields here), as the model is
+    for (int p = 0; p < x.P; ++p) {
+      static const char* wallfn[4] = {"epsilonWallFunction", "nutkWallFunction", "turbulentIntensityKineticEnergyInlet",
+                                      "turbulentMixingLengthDissipationRateInlet"};
+      CHECK(pt[p] < 13 || pt[p] > 16, std::string(wallfn[(pt[p] - 13) & 3]) + " (field '" + f + "'): CPU-A does not implement the "
+            "k-epsilon model's wall functions and turbulent inlets (the HIP library)");
+    }
     CHECK(f == "U" || f == "p" || f == "he" || f == "K" || f == "Y" || f == "T" || f == "rho" || f == "nut", "unknown patch-type field '" + f + "'");
     for (int p = 0; p < x.P; ++p) {
       CHECK(pt[p] >= 0 && pt[p] <= 12 && pt[p] != COUPLED, "unsupported boundary condition code");
@@ -1181,7 +1189,12 @@ int dfmi_set_patch_param(dfmi_ctx* ctx, const char* field, int patch, const char
   return guard([&] {
     Ctx& x = ctx->x;
     CHECK(x.have_bgeom && patch >= 0 && patch < x.P, "bad patch");
-    CHECK(std::string(field) == "p" && std::string(name) == "gamma", "patch parameters: ('p', 'gamma')");
+    const std::string pf(field), pn(name);
+    CHECK(!((pf == "nut" && (pn == "Cmu" || pn == "kappa" || pn == "E")) || (pf == "k" && pn == "intensity") ||
+            (pf == "epsilon" && pn == "mixingLength")),
+          "patch parameter ('" + pf + "', '" + pn + "'): CPU-A does not implement the k-epsilon model's wall functions and "
+          "turbulent inlets (the HIP library)");
+    CHECK(pf == "p" && pn == "gamma", "patch parameters: ('p', 'gamma')");
     double* g = x.f("boundary_p_gamma");
     for (int i = 0; i < x.psize[patch]; ++i) g[x.poff[patch] + i] = value;
   });

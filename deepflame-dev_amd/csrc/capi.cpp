@@ -118,6 +118,20 @@ void ensure_ras_fields(Ctx& x) {
   A.ic.zero(x.stream); A.bc.zero(x.stream);
   for (auto e : {"k", "epsilon"}) if (!x.solver.count(e)) x.solver[e] = SolverCfg{20, 1e-5, 0.0};
 }
+// Wall functions and turbulent inlets: the per-patch parameters with the wall function's defaults and the
+// get-only boundary_yPlus, when one of the four patch types, one of their parameters or that field is first touched. The
+// device tables follow in ras_wall_refresh, and only once a patch carries one of the types (Ctx::wf.in_use).
+void ensure_wall_params(Ctx& x) {   // host only: a parameter set on a context without the patch types allocates nothing
+  if ((int)x.wf.Cmu.size() == x.P) return;
+  x.wf.Cmu.assign(x.P, 0.09); x.wf.kappa.assign(x.P, 0.41); x.wf.E.assign(x.P, 9.8);
+  x.wf.intensity.assign(x.P, 0.0); x.wf.mixingLength.assign(x.P, 0.0);
+}
+void ensure_wall_fields(Ctx& x) {
+  ensure_wall_params(x);
+  if (x.fields.count("boundary_yPlus")) return;
+  ensure_ras_fields(x);
+  alloc_field(x, "boundary_yPlus", x.B, 1, true);
+}
 bool tci_name(const std::string& n) {
   for (const char* s : {"tci_kappa", "tci_tmix", "tci_tauStar", "tci_tc", "RR_eff", "Qdot_eff"}) if (n == s) return true;
   return false;
@@ -174,7 +188,7 @@ void set_ptype(Ctx& x, const std::string& field, const int* pt) {
   std::vector<int8_t> s(x.B, EMPTY);
   for (int p = 0; p < x.P; ++p) {
     const int slots = x.pkind[p] == 2 ? 2 * x.psize[p] : x.psize[p];
-    for (int i = 0; i < slots; ++i) s[x.poff[p] + i] = (int8_t)pt[p];
+    for (int i = 0; i < slots; ++i) s[x.poff[p] + i] = (int8_t)bc_ras_device(pt[p]);
   }
   x.stype[field].upload(s.data(), s.size(), x.stream);
 }
@@ -409,7 +423,11 @@ void ras_solve(Ctx& x, int keq) {
 }
 void ras_correct(Ctx& x) {
   ensure_ras_fields(x);
+  // wall functions and turbulent inlets (nothing without their patch types): k's inletValue first, then
+  // after G and divU the wall cells' epsilon and G, the constraint flags and epsilon's inletValue
+  ras_inlet_k(x);
   ras_production(x);
+  ras_wall_update(x);
   ras_solve(x, 0);
   ras_solve(x, 1);
   ras_nut(x);
@@ -599,7 +617,17 @@ int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* patch_type
                "unknown patch-type field '" + f + "'");
     for (int p = 0; p < x.P; ++p) {
       const int t = patch_type[p];
-      DFMI_CHECK(t >= 0 && t <= 12 && t != COUPLED, "patch " + std::to_string(p) + ": unsupported boundary condition code " + std::to_string(t));
+      DFMI_CHECK(t >= 0 && t <= 16 && t != COUPLED, "patch " + std::to_string(p) + ": unsupported boundary condition code " + std::to_string(t));
+      if (bc_ras_new(t)) {   // the k-epsilon wall functions and turbulent inlets: one field each, plain patches only
+        static const char* wname[4] = {"epsilonWallFunction", "nutkWallFunction", "turbulentIntensityKineticEnergyInlet",
+                                       "turbulentMixingLengthDissipationRateInlet"};
+        static const char* wfield[4] = {"epsilon", "nut", "k", "epsilon"};
+        const std::string wn = wname[t - EPSILON_WALL_FUNCTION], wf = wfield[t - EPSILON_WALL_FUNCTION];
+        DFMI_CHECK(f == wf, "patch " + std::to_string(p) + ": " + wn + " is a condition of the field '" + wf + "', not of '" + f + "'");
+        DFMI_CHECK(x.pkind[p] == 0, "patch " + std::to_string(p) + ": " + wn + " on a " + (x.pkind[p] == 1 ? "cyclic" : "processor") + " patch");
+        DFMI_CHECK(x.pt("calculated")[p] != EMPTY, "patch " + std::to_string(p) + ": " + wn + " on an empty patch");
+        continue;
+      }
       DFMI_CHECK(t != WAVE_TRANSMISSIVE || f == "p", "waveTransmissive is supported for p (the 1D flame's outlet)");
       DFMI_CHECK(t != INLET_OUTLET || f == "U" || f == "p" || f == "Y" || f == "K" || ras,
                  "inletOutlet is supported for U, p, Y, K, k and epsilon (energy needs its own mixed form)");
@@ -613,6 +641,20 @@ int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* patch_type
                  "patch " + std::to_string(p) + ": nut takes zeroGradient, fixedValue, calculated, cyclic, processor, processorCyclic or empty");
     }
     if (ras) ensure_ras_fields(x);
+    if (ras || f == "nut") {
+      // nut belongs to these patch types too: a wall function's slots are formed by correctNut(). The tables are needed
+      // from the first of the four codes on and are dropped with the last
+      bool any = false;
+      for (const char* g : {"k", "epsilon", "nut"}) {
+        if (f == g) { for (int p = 0; p < x.P; ++p) any |= bc_ras_new(patch_type[p]); continue; }
+        auto it = x.ptype.find(g);
+        if (it != x.ptype.end()) for (int t : it->second) any |= bc_ras_new(t);
+      }
+      if (any) ensure_wall_fields(x);
+      if (any || x.wf.in_use) { x.wf.dirty = true; if (!any) x.wf.bits = 0; }
+      x.wf.in_use = any;
+      x.ras.valid = false;
+    }
     set_ptype(x, f, patch_type);
     DFMI_HIP(hipStreamSynchronize(x.stream));
   });
@@ -738,7 +780,21 @@ int dfmi_set_patch_param(dfmi_ctx* ctx, const char* field, int patch, const char
     DFMI_CHECK(x.have_bgeom, "call dfmi_init_constant_fields_boundary first");
     DFMI_CHECK(patch >= 0 && patch < x.P, "patch index out of range");
     const std::string f(field), n(name);
-    DFMI_CHECK(f == "p" && n == "gamma", "patch parameters: ('p', 'gamma') of waveTransmissive");
+    // the k-epsilon wall function's own coefficients and the turbulent inlets' parameters
+    const bool wall = f == "nut" && (n == "Cmu" || n == "kappa" || n == "E");
+    if (wall || (f == "k" && n == "intensity") || (f == "epsilon" && n == "mixingLength")) {
+      DFMI_CHECK(value > 0 && value <= 1.79769313486231570e308,
+                 "patch parameter ('" + f + "', '" + n + "') of patch " + std::to_string(patch) + " must be positive and finite");
+      ensure_wall_params(x);
+      Ctx::WallFn& w = x.wf;
+      (n == "Cmu" ? w.Cmu : n == "kappa" ? w.kappa : n == "E" ? w.E : n == "intensity" ? w.intensity : w.mixingLength)[patch] = value;
+      w.dirty = true;
+      if (wall) x.ras.valid = false;   // boundary_nut of a nutkWallFunction patch depends on them
+      return;
+    }
+    DFMI_CHECK(f == "p" && n == "gamma",
+               "patch parameters: ('p', 'gamma') of waveTransmissive, ('nut', 'Cmu' | 'kappa' | 'E') of nutkWallFunction, "
+               "('k', 'intensity'), ('epsilon', 'mixingLength'); got ('" + f + "', '" + n + "')");
     std::vector<double> g(x.B);
     DFMI_HIP(hipMemcpy(g.data(), x.f("boundary_p_gamma"), x.B * sizeof(double), hipMemcpyDeviceToHost));
     for (int i = 0; i < x.psize[patch]; ++i) g[x.poff[patch] + i] = value;
@@ -803,6 +859,7 @@ int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long cou
     }
     DFMI_CHECK(n != "G" && n != "divU" && n.find("_prebound") == std::string::npos,
                "field '" + n + "' is formed by dfmi_turbulence_correct and cannot be set");
+    DFMI_CHECK(n != "boundary_yPlus", "field 'boundary_yPlus' is formed by dfmi_turbulence_correct and cannot be set");
     DFMI_CHECK(n != "nut", "field 'nut' is formed by dfmi_turbulence_correct and cannot be set (boundary_nut holds the fixed-value slots)");
     DFMI_CHECK(n.rfind("nonorth_", 0) != 0 && n.rfind("boundary_nonorth_", 0) != 0,
                "field '" + n + "' is formed by the library (dfmi_set_scheme \"laplacian\") and cannot be set");
@@ -827,6 +884,7 @@ int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, in
     const std::string n(name ? name : "");
     if (n == "delta" || n == "nut" || n == "boundary_nut") ensure_les_fields(ctx->x);
     if (ras_name(n)) ensure_ras_fields(ctx->x);
+    if (n == "boundary_yPlus") ensure_wall_fields(ctx->x);
     if (tci_name(n)) ensure_tci_fields(ctx->x);
     copy_field(ctx->x, n, host, count, layout, false);
   });
@@ -1125,7 +1183,11 @@ int dfmi_assemble(dfmi_ctx* ctx, const char* eqn) {
     else if (e == "k" || e == "epsilon") {   // from the fields as they stand, no solve in between
       DFMI_CHECK(x.ras.model, "dfmi_assemble: '" + e + "' needs ras.model != 0");
       ensure_ras_fields(x);
+      // a wall-function context: the complete wall update first (epsilon of the wall cells overwritten), the state the
+      // equations see inside correct(); "epsilon" is then the constrained matrix
+      ras_inlet_k(x);
       ras_production(x);
+      ras_wall_update(x);
       ras_assemble(x, e == "k" ? 1 : 0);
     }
     else if (e == "p") {

@@ -33,8 +33,19 @@ __device__ __forceinline__ int xcd_block() {
 enum BC : int8_t {
   ZERO_GRADIENT = 0, FIXED_VALUE = 1, COUPLED = 2, EMPTY = 3, GRADIENT_ENERGY = 4, CALCULATED = 5,
   CYCLIC = 6, PROCESSOR = 7, EXTRAPOLATED = 8, FIXED_ENERGY = 9, PROCESSOR_CYCLIC = 10,
-  WAVE_TRANSMISSIVE = 11, INLET_OUTLET = 12
+  WAVE_TRANSMISSIVE = 11, INLET_OUTLET = 12,
+  // k-epsilon wall functions and turbulent inlets (include/dfmi.h, RAS block). The host keeps these codes
+  // per patch; the device's slot types carry what each behaves as in the assembly (bc_ras_device)
+  EPSILON_WALL_FUNCTION = 13, NUTK_WALL_FUNCTION = 14, TURBULENT_INTENSITY_K_INLET = 15, TURBULENT_MIXING_LENGTH_EPSILON_INLET = 16
 };
+inline bool bc_ras_new(int t) { return t >= EPSILON_WALL_FUNCTION && t <= TURBULENT_MIXING_LENGTH_EPSILON_INLET; }
+// what a slot of one of the four is to every kernel but the wall and inlet-reference ones: the wall functions hold the
+// values those kernels write (fixed values), the inlets are inletOutlet with a re-formed inletValue
+inline int bc_ras_device(int t) {
+  if (t == EPSILON_WALL_FUNCTION || t == NUTK_WALL_FUNCTION) return 1;   // FIXED_VALUE
+  if (t == TURBULENT_INTENSITY_K_INLET || t == TURBULENT_MIXING_LENGTH_EPSILON_INLET) return 12;   // INLET_OUTLET
+  return t;
+}
 
 __host__ __device__ inline bool bc_coupled(int t) { return t == CYCLIC || t == PROCESSOR || t == PROCESSOR_CYCLIC || t == COUPLED; }
 __host__ __device__ inline bool bc_proc(int t) { return t == PROCESSOR || t == PROCESSOR_CYCLIC; }

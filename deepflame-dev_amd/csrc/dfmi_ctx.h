@@ -470,6 +470,19 @@ struct Ctx {
   // RAS k-epsilon (options ras.*, fv_kernels.hip ras_*): the model in force, whether nut belongs to k and epsilon as
   // they stand, and which of k, epsilon, boundary_k, boundary_epsilon the caller has set
   struct Ras { int model = 0; bool valid = false; bool have[4] = {false, false, false, false}; } ras;
+  // k-epsilon wall functions and turbulent inlets. Host, per patch: the wall function's coefficients, the
+  // inlets' intensity and mixing length (0: never set). Device, allocated by the first patch type that needs them
+  // (ras_wall_refresh): per slot the bits WF_* and the slot's patch, per patch the row {Cmu25, Cmu75, kappa, E,
+  // yPlusLam, intensity, mixingLength, 0} of tab, per cell the epsilon equation's constraint flag.
+  enum { WF_EPS_WALL = 1, WF_NUT_WALL = 2, WF_K_INLET = 4, WF_EPS_INLET = 8, WF_TAB = 8 };
+  struct WallFn {
+    std::vector<double> Cmu, kappa, E, intensity, mixingLength;
+    bool in_use = false, dirty = true;
+    int bits = 0;                  // the union of the slots' bits
+    DevBuf<int8_t> sflag, cflag;   // [B], [C]
+    DevBuf<int> spatch;            // [B]
+    DevBuf<double> tab;            // [P][WF_TAB]
+  } wf;
   // the one flag everything downstream of an eddy viscosity reads: either model sets it (the effective fields, the
   // dropped YEqn / EEqn terms, the LES instantiations of the assemblies)
   // combustion closure (options tci.*, chem.hip tci_*): the model in force; bad: the device count of EDC cells without a usable tauStar
@@ -601,6 +614,14 @@ void ras_production(Ctx& x);
 void ras_assemble(Ctx& x, int keq);
 void ras_post_solve(Ctx& x, int keq);
 void ras_nut(Ctx& x);
+// Wall functions and turbulent inlets; every one returns at once in a context without the new patch types.
+// ras_wall_refresh: the refusals (epsilonWallFunction without nutkWallFunction; inlets: an intensity or mixing length never
+// set) and the per-slot / per-patch tables after a change. ras_inlet_k: boundary_k_ref from boundary_U. ras_wall_update:
+// epsilon, G and boundary_epsilon of the wall cells, the constraint flags, boundary_epsilon_ref. ras_correct and
+// dfmi_assemble call ras_inlet_k, ras_production, ras_wall_update in that order.
+void ras_wall_refresh(Ctx& x, bool inlets);
+void ras_inlet_k(Ctx& x);
+void ras_wall_update(Ctx& x);
 // laplacian schemes. nonorth_setup: the non-orthogonal delta coefficients and correction vectors from Sf,
 // mesh_distance and the patch deltas (surfaceInterpolation::makeNonOrthDeltaCoeffs / makeNonOrthCorrectionVectors).
 // nonorth_p_correct: the pEqn's explicit term from the current p / boundary_p -- source = base + div of the face flux

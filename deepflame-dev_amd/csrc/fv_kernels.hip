@@ -2238,31 +2238,64 @@ __global__ void k_ras_sources(long n, int keq, RasCoef q, const double* __restri
 // upwind), the laplacian by the delta coefficients of the scheme in force. The face and slot arithmetic is
 // k_e_assemble's he part; the boundary coefficients k_y_assemble's (inletOutlet included):
 //   diag = ((rdt rho V + d1) - dL) + V Sp;   source = rdt rho_old psi V + V Su
-template <int WT>
+// CON: fvMatrix::setValues folded in (the epsilon equation of a wall-function context; include/dfmi.h).
+// con[c] != 0 marks a constrained cell, whose value v_c is psi[c] (k_ras_wall wrote it there). Each cell forms both
+// L1 - UL and U1 - UL of every face it walks, so it knows A[c][n] without reading lower / upper: the owner writes zeros
+// where either side is constrained; a constrained cell gets source = v_c diag and zero slot coefficients; an
+// unconstrained one walks its faces once more after its source is complete and takes A[c][n] v_n of every constrained
+// neighbour out of it, in the same face order. CON = false is the kernel as it was, op for op.
+template <int WT, bool CON = false>
 __global__ void __launch_bounds__(TPB) k_scalar_assemble(MeshView m, const int8_t* __restrict__ ty,
     const double* __restrict__ psi, const double* __restrict__ bpsi, const double* __restrict__ rho,
     const double* __restrict__ rho_old, const double* __restrict__ phi, const double* __restrict__ bphi,
     const double* __restrict__ D, const double* __restrict__ bD, const double* __restrict__ Su,
     const double* __restrict__ Sp, double* __restrict__ lower, double* __restrict__ upper, double* __restrict__ diag,
     double* __restrict__ src, double* __restrict__ ic, double* __restrict__ bc, MixBC mx,
-    const double* __restrict__ wc, const double* __restrict__ bwc) {
+    const double* __restrict__ wc, const double* __restrict__ bwc, const int8_t* __restrict__ con = nullptr) {
   const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
   if (c >= m.C) return;
   const long B = m.B;
   double d1 = 0.0, dL = 0.0;
   const double Dc = D[c];
+  bool cc = false, cany = false;
+  if constexpr (CON) cc = con[c] != 0;
   each_face<WT>(m, c, [&](int f, int o2, bool own) {
     const double ph = phi[f], w = m.w[f];
     const double wu = wc ? wc[f] : (ph >= 0 ? 1.0 : 0.0);
     const double L1 = -wu * ph, U1 = L1 + ph;
     const double UL = m.dc[f] * ((own ? interp_f(w, Dc, D[o2]) : interp_f(w, D[o2], Dc)) * m.magSf[f]);
-    if (own) { d1 -= L1; lower[f] = L1 - UL; upper[f] = U1 - UL; } else d1 -= U1;
+    if constexpr (CON) {
+      const bool cn = con[o2] != 0;
+      cany = cany || cn;
+      if (own) { d1 -= L1; lower[f] = (cc || cn) ? 0.0 : L1 - UL; upper[f] = (cc || cn) ? 0.0 : U1 - UL; } else d1 -= U1;
+    } else {
+      if (own) { d1 -= L1; lower[f] = L1 - UL; upper[f] = U1 - UL; } else d1 -= U1;
+    }
     dL -= UL;
   });
   const double vol = m.V[c];
-  diag[c] = ((m.rdt * rho[c] * vol + d1) - dL) + vol * Sp[c];
-  src[c] = m.rdt * rho_old[c] * psi[c] * vol + vol * Su[c];
+  const double dg = ((m.rdt * rho[c] * vol + d1) - dL) + vol * Sp[c];
+  diag[c] = dg;
+  if constexpr (CON) {
+    if (cc) src[c] = psi[c] * dg;
+    else {
+      double s = m.rdt * rho_old[c] * psi[c] * vol + vol * Su[c];
+      if (cany)
+        each_face<WT>(m, c, [&](int f, int o2, bool own) {
+          if (con[o2] == 0) return;
+          const double ph = phi[f], w = m.w[f];
+          const double wu = wc ? wc[f] : (ph >= 0 ? 1.0 : 0.0);
+          const double L1 = -wu * ph, U1 = L1 + ph;
+          const double UL = m.dc[f] * ((own ? interp_f(w, Dc, D[o2]) : interp_f(w, D[o2], Dc)) * m.magSf[f]);
+          s -= (own ? U1 - UL : L1 - UL) * psi[o2];   // A[c][n]: upper of an owned face, lower of a neighbour face
+        });
+      src[c] = s;
+    }
+  } else {
+    src[c] = m.rdt * rho_old[c] * psi[c] * vol + vol * Su[c];
+  }
   each_slot(m, ty, c, [&](int b, int t) {
+    if constexpr (CON) if (cc) { ic[b] = 0.0; bc[b] = 0.0; return; }
     const double wu = bwc ? bwc[b] : upwind_b(m, bphi, b);
     const BCoef qc = bcoef_f(t, bpsi[b], wu, m.bdc[b], mx, b, B, 0);
     const BCoef ql = bcoef_f(t, bpsi[b], m.bw[b], m.bdc[b], mx, b, B, 0);
@@ -2271,6 +2304,14 @@ __global__ void __launch_bounds__(TPB) k_scalar_assemble(MeshView m, const int8_
     ic[b] = bphi[b] * qc.vic - pG * ql.gic;
     bc[b] = -bphi[b] * qc.vbc - (-pG * ql.gbc);
   });
+}
+// the constrained cells' source once more, source = v_c diag, where something was added to the source after the
+// assembly (the corrected laplacian's explicit term): each cell writes its own entry
+__global__ void k_ras_constrain_source(long n, const int8_t* __restrict__ con, const double* __restrict__ psi,
+                                       const double* __restrict__ diag, double* __restrict__ src) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= n || con[i] == 0) return;
+  src[i] = psi[i] * diag[i];
 }
 
 // bound(psi, lo) (OpenFOAM-7 bound.C) as a gather from the solved field `pre` (its slots bpre corrected after the solve):
@@ -2311,6 +2352,93 @@ __global__ void k_ras_nut(long n, const int8_t* __restrict__ ty, double Cmu, con
   if (ty && ty[i] != CALCULATED) return;
   const double kc = k[i];
   nut[i] = (Cmu * (kc * kc)) / eps[i];
+}
+
+// ---- wall functions and turbulent inlets (include/dfmi.h, RAS block)
+// What a slot is comes from sflag (Ctx::WF_* bits), its patch's constants from the row tab[WF_TAB * spatch[b]]:
+//   {Cmu25, Cmu75, kappa, E, yPlusLam, intensity, mixingLength}. bdc is the patch's own deltaCoeffs (never the
+// non-orthogonal ones: the two agree on non-coupled slots).
+struct WallTab { const int8_t* sflag; const int* spatch; const double* tab; };
+//   y = 1 / deltaCoeffs;  nuw = boundary_mu / boundary_rho;  yPlus = ((Cmu25 y) sqrt(k_c)) / nuw
+__device__ __forceinline__ double wall_yplus(double Cmu25, double y, double sqrtk, double nuw) { return ((Cmu25 * y) * sqrtk) / nuw; }
+
+// epsilonWallFunction, per cell: the cell's slots of that type in ascending slot order, weight w = 1 / n;
+//   yPlus > yPlusLam:  eps += ((w Cmu75) (k sqrt k)) / (kappa y);  G += ((((w (nutw + nuw)) magGradUw) Cmu25) sqrt k) / (kappa y)
+//   otherwise:         eps += (((w 2) k) nuw) / (y y)
+// with magGradUw = deltaCoeffs |boundary_U - U_c|. epsilon and G of the cell are replaced, boundary_epsilon of those
+// slots takes the cell's value, con[c] says whether the cell is constrained. A cell touches only its own entries.
+// The slot range is each_slot's (cbStart / cbSlot) walked by hand, three times (count, accumulate, write back): the
+// flagged slots are never empty (the codes are refused on empty patches), so each_slot's EMPTY test has nothing to
+// skip. The thread's cell is the plain index, not cell_of / xcd_block: no face is gathered, so there is no locality
+// for a traversal to improve, and the result does not depend on the order.
+__global__ void __launch_bounds__(TPB) k_ras_wall(MeshView m, WallTab t, const double* __restrict__ bdc,
+    const double* __restrict__ k, const double* __restrict__ U, const double* __restrict__ bU,
+    const double* __restrict__ bmu, const double* __restrict__ brho, const double* __restrict__ bnut,
+    double* __restrict__ eps, double* __restrict__ G, double* __restrict__ beps, int8_t* __restrict__ con) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= m.C) return;
+  const int k0 = m.cbStart[c], k1 = m.cbStart[c + 1];
+  int n = 0;
+  for (int i = k0; i < k1; ++i) n += (t.sflag[m.cbSlot[i]] & Ctx::WF_EPS_WALL) ? 1 : 0;
+  con[c] = n ? 1 : 0;
+  if (!n) return;
+  const double w = 1.0 / (double)n;
+  const double kc = k[c], sk = sqrt(kc);
+  const long C = m.C, B = m.B;
+  const double u0 = U[c], u1 = U[C + c], u2 = U[2 * C + c];
+  double e = 0.0, g = 0.0;
+  for (int i = k0; i < k1; ++i) {
+    const int b = m.cbSlot[i];
+    if (!(t.sflag[b] & Ctx::WF_EPS_WALL)) continue;
+    const double* q = t.tab + Ctx::WF_TAB * t.spatch[b];
+    const double Cmu25 = q[0], Cmu75 = q[1], kappa = q[2], ypl = q[4];
+    const double dcb = bdc[b], y = 1.0 / dcb, nuw = bmu[b] / brho[b];
+    const double yp = wall_yplus(Cmu25, y, sk, nuw);
+    if (yp > ypl) {
+      const double dx = bU[b] - u0, dy = bU[B + b] - u1, dz = bU[2 * B + b] - u2;
+      const double mg = dcb * sqrt((dx * dx + dy * dy) + dz * dz);
+      e += ((w * Cmu75) * (kc * sk)) / (kappa * y);
+      g += ((((w * (bnut[b] + nuw)) * mg) * Cmu25) * sk) / (kappa * y);
+    } else {
+      e += (((w * 2.0) * kc) * nuw) / (y * y);
+    }
+  }
+  eps[c] = e;
+  G[c] = g;
+  for (int i = k0; i < k1; ++i) {
+    const int b = m.cbSlot[i];
+    if (t.sflag[b] & Ctx::WF_EPS_WALL) beps[b] = e;
+  }
+}
+// nutkWallFunction, per slot: boundary_nut = yPlus > yPlusLam ? nuw ((yPlus kappa) / log(E yPlus) - 1) : 0, and
+// boundary_yPlus (zero on every other slot)
+__global__ void k_ras_nut_wall(long n, WallTab t, const int* __restrict__ bfc, const double* __restrict__ bdc,
+                               const double* __restrict__ k, const double* __restrict__ bmu, const double* __restrict__ brho,
+                               double* __restrict__ bnut, double* __restrict__ byp) {
+  const long b = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  if (!(t.sflag[b] & Ctx::WF_NUT_WALL)) { byp[b] = 0.0; return; }
+  const double* q = t.tab + Ctx::WF_TAB * t.spatch[b];
+  const double Cmu25 = q[0], kappa = q[2], E = q[3], ypl = q[4];
+  const double y = 1.0 / bdc[b], nuw = bmu[b] / brho[b];
+  const double yp = wall_yplus(Cmu25, y, sqrt(k[bfc[b]]), nuw);
+  byp[b] = yp;
+  bnut[b] = yp > ypl ? nuw * ((yp * kappa) / log(E * yp) - 1.0) : 0.0;
+}
+// the turbulent inlets' inletValue, per slot. which = WF_K_INLET: k_ref = (1.5 (I I)) ((Ux Ux + Uy Uy) + Uz Uz) of
+// boundary_U; which = WF_EPS_INLET: eps_ref = (Cmu75 / L) (kb sqrt(kb)) of boundary_k, Cmu75 of ras.Cmu
+__global__ void k_ras_inlet_ref(long n, int which, WallTab t, double Cmu75, const double* __restrict__ bU,
+                                const double* __restrict__ bk, double* __restrict__ ref) {
+  const long b = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (b >= n || !(t.sflag[b] & which)) return;
+  const double* q = t.tab + Ctx::WF_TAB * t.spatch[b];
+  if (which == Ctx::WF_K_INLET) {
+    const double I = q[5], ux = bU[b], uy = bU[n + b], uz = bU[2 * n + b];
+    ref[b] = (1.5 * (I * I)) * ((ux * ux + uy * uy) + uz * uz);
+  } else {
+    const double L = q[6], kb = bk[b];
+    ref[b] = (Cmu75 / L) * (kb * sqrt(kb));
+  }
 }
 
 // ------------------------------------------------------------------ non-orthogonal laplacians
@@ -3207,6 +3335,17 @@ void ras_assemble(Ctx& x, int keq) {
   }
   const double *w, *bw;
   ras_weights(x, kind, keq ? x.sch.k_tk : x.sch.k_teps, nm, g, bg, w, bw);
+  // epsilonWallFunction: the epsilon matrix is constrained on the wall cells (an instantiation of its own)
+  const bool con = !keq && (x.wf.bits & Ctx::WF_EPS_WALL);
+  if (con) {
+    const int8_t* cf = x.wf.cflag.p;
+#define SCALAR_CON(WT) \
+    LAUNCH_AS("k_scalar_assemble", (k_scalar_assemble<WT, true>), x.C, m, ty, x.f(nm), x.f(bn), x.f("rho"), x.f("rho_old"), \
+              x.f("phi"), x.f("boundary_phi"), x.f("ras_D"), x.f("boundary_ras_D"), x.f("ras_Su"), x.f("ras_Sp"), A.lower.p, \
+              A.upper.p, A.diag.p, A.source.p, A.ic.p, A.bc.p, mixbc(x, nm), w, bw, cf)
+    if (face_hex(x)) SCALAR_CON(-1); else if (face_rows(x)) SCALAR_CON(6); else SCALAR_CON(0);
+#undef SCALAR_CON
+  } else
   LAUNCH_W(k_scalar_assemble, x.C, m, ty, x.f(nm), x.f(bn), x.f("rho"), x.f("rho_old"), x.f("phi"), x.f("boundary_phi"),
            x.f("ras_D"), x.f("boundary_ras_D"), x.f("ras_Su"), x.f("ras_Sp"), A.lower.p, A.upper.p, A.diag.p, A.source.p,
            A.ic.p, A.bc.p, mixbc(x, nm), w, bw);
@@ -3216,6 +3355,7 @@ void ras_assemble(Ctx& x, int keq) {
     a.gam = x.f("ras_D"); a.bgam = x.f("boundary_ras_D");
     a.src = A.source.p;
     LAUNCH_NO(1, NO_SHARED, ty, a);
+    if (con) LAUNCH(k_ras_constrain_source, x.C, (long)x.C, x.wf.cflag.p, x.f(nm), A.diag.p, A.source.p);
   }
 }
 // after the solve: the field's boundary values and halo (fvMatrix::solve's correctBoundaryConditions), then bound()
@@ -3232,6 +3372,7 @@ void ras_post_solve(Ctx& x, int keq) {
   LAUNCH(k_ras_bound_slots, x.B, (long)x.B, lo, x.f(bn));
   halo_fields(x, {nm});
 }
+static WallTab wall_tab(Ctx& x) { return {x.wf.sflag.p, x.wf.spatch.p, x.wf.tab.p}; }
 // correctNut(): nut = Cmu k^2 / epsilon on cells and on nut's `calculated` slots, boundary_nut by nut's patch types, halo
 void ras_nut(Ctx& x) {
   ras_check_set(x);
@@ -3240,8 +3381,76 @@ void ras_nut(Ctx& x) {
   LAUNCH(k_ras_nut, x.C, (long)x.C, (const int8_t*)nullptr, Cmu, x.f("k"), x.f("epsilon"), x.f("nut"));
   LAUNCH(k_ras_nut, x.B, (long)x.B, x.st(tn), Cmu, x.f("boundary_k"), x.f("boundary_epsilon"), x.f("boundary_nut"));
   k_bc_correct(x, tn, x.f("nut"), x.f("boundary_nut"), 1);
+  ras_wall_refresh(x, false);
+  if (x.wf.bits & Ctx::WF_NUT_WALL)   // nutkWallFunction slots from the current k: a launch of its own
+    LAUNCH(k_ras_nut_wall, x.B, (long)x.B, wall_tab(x), x.bfc.p, x.bdc.p, x.f("k"), x.f("boundary_mu"), x.f("boundary_rho"),
+           x.f("boundary_nut"), x.f("boundary_yPlus"));
   halo_fields(x, {"nut"});
   x.ras.valid = true;
+}
+// ---- wall functions and turbulent inlets
+// yPlusLam of (kappa, E): ypl = 11, then ten times ypl = log(max(E ypl, 1)) / kappa
+static double y_plus_lam(double kappa, double E) {
+  double ypl = 11.0;
+  for (int i = 0; i < 10; ++i) ypl = std::log(std::max(E * ypl, 1.0)) / kappa;
+  return ypl;
+}
+void ras_wall_refresh(Ctx& x, bool inlets) {
+  Ctx::WallFn& w = x.wf;
+  if (!w.in_use) return;
+  auto code = [&](const char* f, int p) { auto it = x.ptype.find(f); return it == x.ptype.end() ? -1 : it->second[p]; };
+  for (int p = 0; p < x.P; ++p) {
+    DFMI_CHECK(code("epsilon", p) != EPSILON_WALL_FUNCTION || code("nut", p) == NUTK_WALL_FUNCTION,
+               "patch " + std::to_string(p) + ": epsilonWallFunction for epsilon needs nutkWallFunction for nut on the same patch");
+    if (!inlets) continue;
+    DFMI_CHECK(code("k", p) != TURBULENT_INTENSITY_K_INLET || w.intensity[p] > 0,
+               "patch " + std::to_string(p) + ": turbulentIntensityKineticEnergyInlet without an intensity (dfmi_set_patch_param 'k', 'intensity')");
+    DFMI_CHECK(code("epsilon", p) != TURBULENT_MIXING_LENGTH_EPSILON_INLET || w.mixingLength[p] > 0,
+               "patch " + std::to_string(p) + ": turbulentMixingLengthDissipationRateInlet without a mixing length (dfmi_set_patch_param 'epsilon', 'mixingLength')");
+  }
+  if (!w.dirty) return;
+  std::vector<int8_t> sf((size_t)std::max<long>(x.B, 1), 0);
+  std::vector<int> sp((size_t)std::max<long>(x.B, 1), 0);
+  std::vector<double> tab((size_t)Ctx::WF_TAB * std::max<long>(x.P, 1), 0.0);
+  w.bits = 0;
+  for (int p = 0; p < x.P; ++p) {
+    int bits = 0;
+    if (code("epsilon", p) == EPSILON_WALL_FUNCTION) bits |= Ctx::WF_EPS_WALL;
+    if (code("nut", p) == NUTK_WALL_FUNCTION) bits |= Ctx::WF_NUT_WALL;
+    if (code("k", p) == TURBULENT_INTENSITY_K_INLET) bits |= Ctx::WF_K_INLET;
+    if (code("epsilon", p) == TURBULENT_MIXING_LENGTH_EPSILON_INLET) bits |= Ctx::WF_EPS_INLET;
+    w.bits |= bits;
+    const int slots = x.pkind[p] == 2 ? 2 * x.psize[p] : x.psize[p];
+    for (int i = 0; i < slots; ++i) { sf[x.poff[p] + i] = (int8_t)bits; sp[x.poff[p] + i] = p; }
+    double* q = &tab[(size_t)Ctx::WF_TAB * p];
+    const double Cmu25 = std::sqrt(std::sqrt(w.Cmu[p]));
+    q[0] = Cmu25; q[1] = Cmu25 * std::sqrt(w.Cmu[p]); q[2] = w.kappa[p]; q[3] = w.E[p];
+    q[4] = y_plus_lam(w.kappa[p], w.E[p]); q[5] = w.intensity[p]; q[6] = w.mixingLength[p];
+  }
+  w.sflag.upload(sf, x.stream); w.spatch.upload(sp, x.stream); w.tab.upload(tab, x.stream);
+  if (w.cflag.n != (size_t)std::max<long>(x.C, 1)) { w.cflag.alloc((size_t)std::max<long>(x.C, 1)); w.cflag.zero(x.stream); }
+  DFMI_HIP(hipStreamSynchronize(x.stream));   // the host vectors go out of scope
+  w.dirty = false;
+}
+void ras_inlet_k(Ctx& x) {
+  ras_wall_refresh(x, true);
+  if (!(x.wf.bits & Ctx::WF_K_INLET)) return;
+  LAUNCH(k_ras_inlet_ref, x.B, (long)x.B, (int)Ctx::WF_K_INLET, wall_tab(x), 0.0, x.f("boundary_U"), x.f("boundary_k"),
+         x.f("boundary_k_ref"));
+}
+void ras_wall_update(Ctx& x) {
+  if (x.wf.bits & Ctx::WF_EPS_WALL) {
+    LAUNCH(k_ras_wall, x.C, x.view(), wall_tab(x), x.bdc.p, x.f("k"), x.f("U"), x.f("boundary_U"), x.f("boundary_mu"),
+           x.f("boundary_rho"), x.f("boundary_nut"), x.f("epsilon"), x.f("G"), x.f("boundary_epsilon"), x.wf.cflag.p);
+    // several ranks: the wall cells' new epsilon on the processor slots (the epsilon gradient of the limiter and of the
+    // corrected laplacian reads the cell across a processor face; ras_production's halo carried the old values)
+    halo_fields(x, {"epsilon"});
+  }
+  if (x.wf.bits & Ctx::WF_EPS_INLET) {
+    const double Cmu = x.opt("ras.Cmu"), Cmu75 = std::sqrt(std::sqrt(Cmu)) * std::sqrt(Cmu);
+    LAUNCH(k_ras_inlet_ref, x.B, (long)x.B, (int)Ctx::WF_EPS_INLET, wall_tab(x), Cmu75, x.f("boundary_U"), x.f("boundary_k"),
+           x.f("boundary_epsilon_ref"));
+  }
 }
 #undef LAUNCH_GRAD
 #undef LAUNCH_NO

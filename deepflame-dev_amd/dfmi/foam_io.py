@@ -79,9 +79,10 @@ _TURBULENCE_REFUSED = ("epsilonWallFunction", "turbulentMixingLengthDissipationR
 
 
 def turbulence_patch_types(field: str, types: dict) -> dict:
-    """{patch: type name} of a k, epsilon or nut file (read_field's second result) with kqRWallFunction mapped to
-    zeroGradient; epsilonWallFunction, the nut*WallFunction family and the turbulent inlet conditions raise a ValueError
-    that names the field, the patch and the type"""
+    """The strict mapper: {patch: type name} of a k, epsilon or nut file (read_field's second result) with
+    kqRWallFunction mapped to zeroGradient; epsilonWallFunction, the nut*WallFunction family and the turbulent inlet
+    conditions raise a ValueError that names the field, the patch and the type. It serves callers that set no patch
+    parameters; turbulence_boundary (below) maps the wall functions and turbulent inlets the device implements."""
     out = {}
     for patch, t in types.items():
         if t == "kqRWallFunction":
@@ -90,6 +91,91 @@ def turbulence_patch_types(field: str, types: dict) -> dict:
             raise ValueError(f"{field}: patch {patch}: boundary condition {t} is not supported "
                              "(wall functions and turbulent inlet conditions are not implemented)")
         out[patch] = t
+    return out
+
+
+def read_boundary_entries(path: str):
+    """({patch: {keyword: text}}, internalField text or None) of a field file: every `keyword value;` entry of each
+    patch dictionary as text, "type" included, in file order"""
+    txt = re.sub(r"/\*.*?\*/", "", _open(path).read(), flags=re.S)
+    txt = re.sub(r"//.*", "", txt)
+    mi = re.search(r"internalField\s+([^;]+);", txt)
+    b = txt.find("boundaryField")
+    out = {}
+    if b >= 0:
+        for pm in re.finditer(r"(\w+)\s*\{([^{}]*)\}", txt[b + len("boundaryField"):]):
+            out[pm.group(1)] = {k: v.strip() for k, v in re.findall(r"(\w+)\s+([^;]+);", pm.group(2))}
+    return out, (mi.group(1).strip() if mi else None)
+
+
+# The wall functions and turbulent inlets of the k-epsilon model on the device (include/dfmi.h, RAS block; DESIGN.md 16):
+# type -> (the field it belongs to, the parameters read from its patch dictionary). The coefficients in 0/epsilon's
+# epsilonWallFunction entries are not read: OpenFOAM-7 takes them from the patch's nutkWallFunction.
+_TURBULENCE_MAPPED = {
+    "epsilonWallFunction": ("epsilon", ()),
+    "nutkWallFunction": ("nut", ("Cmu", "kappa", "E")),
+    "turbulentIntensityKineticEnergyInlet": ("k", ("intensity",)),
+    "turbulentMixingLengthDissipationRateInlet": ("epsilon", ("mixingLength",)),
+}
+_TURBULENCE_REQUIRED = ("intensity", "mixingLength")
+
+
+def _uniform(where: str, text: str, internal: str | None) -> float:
+    if text == "$internalField":
+        if internal is None:
+            raise ValueError(f"{where}: value $internalField, but the file's internalField was not given")
+        text = internal
+    mo = re.fullmatch(r"uniform\s+(\S+)", text)
+    if not mo:
+        raise ValueError(f"{where}: value {text!r} is not `uniform <number>`")
+    return float(mo.group(1))
+
+
+def turbulence_boundary(field: str, types: dict, entries: dict, internal_field: str | None = None) -> dict:
+    """{"types": {patch: code}, "params": {patch: {name: number}}, "values": {patch: number or None}} of a k, epsilon
+    or nut file. types: {patch: type name}; entries: {patch: {keyword: text}} (read_boundary_entries). The codes are
+    dfmi.mesh's; kqRWallFunction is zeroGradient; the wall functions and turbulent inlets map to their own codes with the
+    parameters their patch dictionaries carry (Cmu / kappa / E of 0/nut where given, intensity, mixingLength: required),
+    ready for Context.set_patch_types and Context.set_patch_param. `value uniform v` and `value $internalField` (resolved
+    with internal_field, the file's internalField text) are returned per patch. The rest of the nut*WallFunction family,
+    wedge, a mapped type in the wrong file and every unknown type raise a ValueError naming field, patch and type."""
+    from .mesh import BC_NAMES
+    out = {"types": {}, "params": {}, "values": {}}
+    for patch, t in types.items():
+        where = f"{field}: patch {patch}"
+        ent = entries.get(patch, {})
+        if t == "kqRWallFunction":
+            code = BC_NAMES["zeroGradient"]
+        elif t in _TURBULENCE_MAPPED:
+            owner, names = _TURBULENCE_MAPPED[t]
+            if owner != field:
+                raise ValueError(f"{where}: boundary condition {t} belongs to the field {owner}")
+            code = BC_NAMES[t]
+            par = {}
+            for n in names:
+                if n in ent:
+                    try:
+                        par[n] = float(ent[n])
+                    except ValueError:
+                        raise ValueError(f"{where}: {t}: {n} {ent[n]!r} is not a number") from None
+                    if not (par[n] > 0 and np.isfinite(par[n])):
+                        raise ValueError(f"{where}: {t}: {n} {ent[n]} must be positive and finite")
+                elif n in _TURBULENCE_REQUIRED:
+                    raise ValueError(f"{where}: {t} without a {n} entry")
+            if par:
+                out["params"][patch] = par
+        elif t.startswith("nut") and t.endswith("WallFunction"):
+            raise ValueError(f"{where}: boundary condition {t} is not supported (of the nut wall functions only "
+                             "nutkWallFunction is implemented)")
+        elif t == "wedge":
+            raise ValueError(f"{where}: boundary condition wedge is not supported (a transform condition on U and on "
+                             "every gradient)")
+        elif t in BC_NAMES and t != "coupled":
+            code = BC_NAMES[t]
+        else:
+            raise ValueError(f"{where}: boundary condition {t} is not supported")
+        out["types"][patch] = code
+        out["values"][patch] = _uniform(where, ent["value"], internal_field) if "value" in ent else None
     return out
 
 

@@ -38,8 +38,16 @@ FIXED_ENERGY = 9
 PROCESSOR_CYCLIC = 10
 WAVE_TRANSMISSIVE = 11   # mixed conditions beyond the reference GPU enum (include/dfmi.h)
 INLET_OUTLET = 12
+# k-epsilon wall functions and turbulent inlets (include/dfmi.h, RAS block): one field each -- epsilon, nut, k, epsilon
+EPSILON_WALL_FUNCTION = 13
+NUTK_WALL_FUNCTION = 14
+TURBULENT_INTENSITY_K_INLET = 15
+TURBULENT_MIXING_LENGTH_EPSILON_INLET = 16
 
 BC_NAMES = {
+    "epsilonWallFunction": EPSILON_WALL_FUNCTION, "nutkWallFunction": NUTK_WALL_FUNCTION,
+    "turbulentIntensityKineticEnergyInlet": TURBULENT_INTENSITY_K_INLET,
+    "turbulentMixingLengthDissipationRateInlet": TURBULENT_MIXING_LENGTH_EPSILON_INLET,
     "zeroGradient": ZERO_GRADIENT, "fixedValue": FIXED_VALUE, "coupled": COUPLED,
     "empty": EMPTY, "gradientEnergy": GRADIENT_ENERGY, "calculated": CALCULATED,
     "cyclic": CYCLIC, "processor": PROCESSOR, "extrapolated": EXTRAPOLATED,

@@ -242,11 +242,12 @@ def read_case_turbulence(path: str, chemistry_path: str | None = None) -> dict:
     return read_turbulence_properties(path, chemistry_path)
 
 
-def apply_ras(ctx, m, settings: dict, patch_types: dict | None = None, k=None, epsilon=None) -> None:
+def apply_ras(ctx, m, settings: dict, patch_types: dict | None = None, k=None, epsilon=None, patch_params: dict | None = None) -> None:
     """the options ras.* on a context that has been set up (case.setup_context), the patch types of "k", "epsilon" and
     "nut" where patch_types has them, and, where given, the cell fields k and epsilon with boundary values as
     correctBoundaryConditions would leave them (zeroGradient / coupled; fixed-value slots are the caller's to set).
-    settings: parse_ras_properties' result."""
+    settings: parse_ras_properties' result. patch_params: {field: {patch index: {name: value}}} of the wall functions and
+    turbulent inlets (foam_io.turbulence_boundary's "params" by patch index), set after the types."""
     from . import case
     ctx.set_option("les.model", 0)
     for key in ("Cmu", "C1", "C2", "C3", "sigmak", "sigmaEps", "kMin", "epsilonMin", "Prt", "Sct"):
@@ -255,6 +256,10 @@ def apply_ras(ctx, m, settings: dict, patch_types: dict | None = None, k=None, e
     for f in ("k", "epsilon", "nut"):
         if patch_types is not None and patch_types.get(f) is not None:
             ctx.set_patch_types(f, patch_types[f])
+    for f, per_patch in (patch_params or {}).items():
+        for patch, par in per_patch.items():
+            for name, v in par.items():
+                ctx.set_patch_param(f, int(patch), name, v)
     for name, v in (("k", k), ("epsilon", epsilon)):
         if v is not None:
             v = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (m.n_cells,)))

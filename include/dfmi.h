@@ -152,9 +152,19 @@ int dfmi_set_traversal(dfmi_ctx* ctx, const int* order);
  * dfEEqn.cu setConstantFields, dfThermo.cu setConstantFields). field in
  * {"U","p","he","K","Y","T","rho","nut","k","epsilon"}; patch_type[num_patches]. "nut" (LES / RAS, below) takes zeroGradient, fixedValue,
  * calculated, cyclic, processor, processorCyclic and empty; not set, it is "calculated" on every non-coupled patch
- * (OpenFOAM's default for nut: the stored boundary_nut is kept, zero unless set) */
+ * (OpenFOAM's default for nut: the stored boundary_nut is kept, zero unless set).
+ * The k-epsilon wall functions and turbulent inlets (RAS block below) have codes of their own, each for one field, on plain
+ * (not cyclic, processor or empty) patches only; any other field or patch kind is refused by name:
+ *   13 epsilonWallFunction (epsilon), 14 nutkWallFunction (nut), 15 turbulentIntensityKineticEnergyInlet (k),
+ *   16 turbulentMixingLengthDissipationRateInlet (epsilon).
+ * Setting the patch types of k, epsilon or nut invalidates nut as writing k does. */
 int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* patch_type);
-/* a patch parameter of a mixed condition: (field "p", name "gamma") of waveTransmissive */
+/* a patch parameter, positive and finite: (field "p", name "gamma") of waveTransmissive; ("nut", "Cmu" | "kappa" | "E") of
+ * nutkWallFunction (defaults 0.09, 0.41, 9.8: the wall function's own coefficients, which the patch's epsilonWallFunction
+ * reads too -- the copies in a case's 0/epsilon are ignored, as in OpenFOAM-7; setting one invalidates nut);
+ * ("k", "intensity") of turbulentIntensityKineticEnergyInlet; ("epsilon", "mixingLength") of
+ * turbulentMixingLengthDissipationRateInlet (both without a default: never set on a patch of that type is an error at the
+ * first dfmi_turbulence_correct). Anything else is refused by name. */
 int dfmi_set_patch_param(dfmi_ctx* ctx, const char* field, int patch, const char* name, double value);
 /* dfYEqn inertIndex (YEqn.H:119-131) */
 int dfmi_set_inert_index(dfmi_ctx* ctx, int inert_index);
@@ -174,7 +184,8 @@ int dfmi_thermo_load(dfmi_ctx* ctx, const char* thermo_coeff_file);
  *        boundary_{U,p,Y,K}_ref (inletOutlet inletValue), boundary_p_vf (waveTransmissive valueFraction),
  *        boundary_p_gamma, chem_stats [3][C]. count = values per component.
  *        LES: delta (cells; positive), nut (cells; get only), boundary_nut (set: the fixedValue / calculated slots).
- *        RAS: k epsilon (cells), boundary_{k,epsilon}, boundary_{k,epsilon}_ref; get only: G divU k_prebound epsilon_prebound.
+ *        RAS: k epsilon (cells), boundary_{k,epsilon}, boundary_{k,epsilon}_ref; get only: G divU k_prebound epsilon_prebound,
+ *        boundary_yPlus (the nutkWallFunction slots' yPlus, zero elsewhere).
  *        Combustion closure: tci_tc (cells); get only: tci_kappa tci_tmix tci_tauStar Qdot_eff (cells), RR_eff (species). */
 int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long count, int layout);
 int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, int layout);
@@ -207,7 +218,7 @@ int dfmi_E_process(dfmi_ctx* ctx);              /* dfEEqn::process (dfEEqn.cu:10
  *
  * ---- RAS k-epsilon (ras.model = 1): the same call is kEpsilon::correct(). The statement below is the definition: it
  * restates OpenFOAM-7 kEpsilon::correct() / correctNut() and bound() for the compressible solver (alpha = 1, no
- * fvOptions, no wall functions). Options (dfmi_set_option; all positive and finite, C3 any finite value):
+ * fvOptions; the wall functions and turbulent inlets follow at the end of this block). Options (dfmi_set_option; all positive and finite, C3 any finite value):
  *   ras.model  0 none (default) | 1 kEpsilon          (ras.model != 0 together with les.model != 0 is refused)
  *   ras.Cmu 0.09, ras.C1 1.44, ras.C2 1.92, ras.C3 0, ras.sigmak 1.0, ras.sigmaEps 1.3,
  *   ras.kMin 1e-15, ras.epsilonMin 1e-15, ras.Prt 1, ras.Sct 1     (Prt / Sct replace les.Prt / les.Sct in RAS mode)
@@ -243,7 +254,53 @@ int dfmi_E_process(dfmi_ctx* ctx);              /* dfEEqn::process (dfEEqn.cu:10
  * before bound()); patch types "k" and "epsilon". nut belongs to k and epsilon: writing either, a boundary counterpart,
  * ras.model or a coefficient invalidates it; dfmi_time_step and the per-equation entries then run correctNut() only
  * (turbulence->validate()), never the equations. Solver names "epsilon" and "k" (dfmi_set_solver / _stats / _work);
- * dfmi_assemble / dfmi_get_matrix take "epsilon" and "k": each is formed from the fields as they stand, no solve between. */
+ * dfmi_assemble / dfmi_get_matrix take "epsilon" and "k": each is formed from the fields as they stand, no solve between.
+ *
+ * ---- wall functions and turbulent inlets (patch-type codes 13-16, dfmi_set_patch_types; parameters, dfmi_set_patch_param).
+ * The statement below is the definition; it restates OpenFOAM-7's epsilonWallFunction, nutkWallFunction,
+ * turbulentIntensityKineticEnergyInlet and turbulentMixingLengthDissipationRateInlet in the compressible solver
+ * (kqRWallFunction is zeroGradient; alphatWallFunction needs nothing: alphaEff = alpha + rho nut / Prt with the wall
+ * function's boundary_nut already is it). A context without these patch types launches none of their kernels and
+ * allocates nothing for them. One cost reaches every RAS context: dfmi_set_patch_types of k, epsilon or nut invalidates
+ * nut whatever the codes, so the next validation runs correctNut() (the two k_ras_nut launches) once more, with the same
+ * result; in LES and laminar contexts that flag is not read.
+ * Per wall patch, on the host, from its ("nut", ...) parameters:
+ *   Cmu25 = sqrt(sqrt(Cmu));   Cmu75 = Cmu25 * sqrt(Cmu);   yPlusLam: ypl = 11, then ten times ypl = log(max(E * ypl, 1)) / kappa
+ * Per wall slot b of cell c:
+ *   y = 1 / deltaCoeffs_b  (the patch's own deltaCoeffs under every laplacian scheme);   nuw = boundary_mu_b / boundary_rho_b
+ *   yPlus = ((Cmu25 * y) * sqrt(k_c)) / nuw
+ * nutkWallFunction, wherever boundary_nut is formed (correctNut() at the end of this call and on the validation path), from
+ * the current k:
+ *   boundary_nut_b = yPlus > yPlusLam ? nuw * ((yPlus * kappa) / log(E * yPlus) - 1) : 0;   boundary_yPlus_b = yPlus
+ * epsilonWallFunction, after G and divU are formed and before the epsilon equation, from the old k and the boundary_nut as
+ * stored. A patch that is epsilonWallFunction for epsilon must be nutkWallFunction for nut: otherwise this call and the
+ * validation path fail, naming the patch. For every cell c with n >= 1 slots of this type (over all such patches):
+ * w = 1 / n, G[c] and epsilon[c] are reset to 0, then its slots are accumulated in ascending slot order,
+ *   yPlus > yPlusLam:  epsilon[c] += ((w * Cmu75) * (k_c * sqrt(k_c))) / (kappa * y)
+ *                      G[c] += ((((w * (boundary_nut_b + nuw)) * magGradUw) * Cmu25) * sqrt(k_c)) / (kappa * y)
+ *   otherwise:         epsilon[c] += (((w * 2) * k_c) * nuw) / (y * y)
+ *   magGradUw = deltaCoeffs_b * sqrt((dx * dx + dy * dy) + dz * dz),  d = boundary_U_b - U_c
+ * and boundary_epsilon_b = epsilon[c] on those slots, which are fixed values from there on (the post-solve correction
+ * leaves them; bound()'s slot pass applies). The kEqn sees the modified G.
+ * The constraint (fvMatrix::setValues): the epsilon matrix is constrained on those cells after assembly, v_c = epsilon[c].
+ *   A constrained cell: source = v_c * diag; its off-diagonals and the internalCoeffs / boundaryCoeffs of all its slots are 0.
+ *   An unconstrained cell: source -= A[c][n] * v_n and A[c][n] = 0, once per constrained neighbour n across an internal
+ *   face, in the sequential face order (neighbour faces ascending, then owned faces), after the source is otherwise
+ *   complete (under the corrected laplacian the explicit non-orthogonal term is added after it).
+ *   Nothing is moved across a coupled slot: the cell across keeps its coupling and reads v through the halo or the cyclic column.
+ * After the solve a constrained cell holds v_c to within 4 * 2^-52 relative (the even-odd recovery forms (v d) / d).
+ * Turbulent inlets: both are inletOutlet (valueFraction = 1 - pos0(phi), refGrad 0) with an inletValue re-formed at each call,
+ *   k:        boundary_k_ref_b = (1.5 * (I * I)) * ((Ux * Ux + Uy * Uy) + Uz * Uz)  of boundary_U, first thing in the call
+ *   epsilon:  boundary_epsilon_ref_b = (Cmu75 / L) * (kb * sqrt(kb)),  kb = boundary_k_b as it stands before the epsilon
+ *             equation, Cmu75 formed as above from ras.Cmu
+ * and coefficients, post-solve correction and bound() bitwise those of inletOutlet with those inletValues set by hand.
+ * Order of the call: k's inletValue; G and divU; the wall update and epsilon's inletValue; the epsilon equation assembled
+ * and constrained, solved, bound; the k equation, solved, bound; correctNut() with the wall slots. Several ranks: the wall
+ * update is rank-local; where a patch is epsilonWallFunction the new epsilon goes through the field halo once more before
+ * the assembly (a collective: every rank carries every physical patch, of size zero where it has none of its faces, as
+ * decomposePar leaves them, and sets the same types on it).
+ * dfmi_assemble("epsilon" | "k") in such a context runs the complete wall update first, the overwrite of epsilon in the
+ * wall cells included: the state the equations see inside this call. "epsilon" returns the constrained matrix. */
 int dfmi_turbulence_correct(dfmi_ctx* ctx);
 int dfmi_thermo_correct(dfmi_ctx* ctx);         /* dfThermo::correctThermo (dfThermo.cu:572-671) */
 int dfmi_thermo_update_energy(dfmi_ctx* ctx);   /* he, psi, rho, transport from T (dfThermo::updateEnergy) */
