@@ -1212,6 +1212,14 @@ int dfmi_thermo_set_coeffs(dfmi_ctx* ctx, int S, const double* W, const double* 
   });
 }
 int dfmi_thermo_load(dfmi_ctx*, const char*) { return guard([&] { throw Error("dfmi (CPU-A): use dfmi_thermo_set_coeffs"); }); }
+// equation of state: the ideal gas is CPU-A's own; the Peng-Robinson model is the HIP library's alone
+int dfmi_thermo_set_eos(dfmi_ctx* ctx, int model, int, const double*, const double*, const double*) {
+  return guard([&] {
+    CHECK(ctx, "null context");
+    CHECK(model == 0 || model == 1, "dfmi_thermo_set_eos: model must be 0 (ideal gas) or 1 (Peng-Robinson)");
+    CHECK(model == 0, "dfmi_thermo_set_eos: model = 1: CPU-A does not implement the Peng-Robinson equation of state (the HIP library)");
+  });
+}
 
 int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long count, int layout) {
   return guard([&] {

@@ -132,6 +132,14 @@ void ensure_wall_fields(Ctx& x) {
   ensure_ras_fields(x);
   alloc_field(x, "boundary_yPlus", x.B, 1, true);
 }
+// Equation of state (dfmi_thermo_set_eos): the thermo's own density, OpenFOAM's thermo.rho_. Allocated when an equation of
+// state, or the field itself, is first touched: an ideal-gas context allocates what it always did.
+void ensure_eos_fields(Ctx& x) {
+  if (x.fields.count("rho_thermo")) return;
+  DFMI_CHECK(x.have_sizes, "call dfmi_set_constant_values first");
+  alloc_field(x, "rho_thermo", x.C, 1, false);
+  alloc_field(x, "boundary_rho_thermo", x.B, 1, true);
+}
 bool tci_name(const std::string& n) {
   for (const char* s : {"tci_kappa", "tci_tmix", "tci_tauStar", "tci_tc", "RR_eff", "Qdot_eff"}) if (n == s) return true;
   return false;
@@ -828,6 +836,37 @@ int dfmi_thermo_set_coeffs(dfmi_ctx* ctx, int S, const double* W, const double* 
   });
 }
 
+int dfmi_thermo_set_eos(dfmi_ctx* ctx, int model, int S, const double* a, const double* b, const double* w) {
+  return guard([&] {
+    DFMI_CHECK(ctx, "null context");
+    Ctx& x = ctx->x;
+    DFMI_CHECK(model == 0 || model == 1, "dfmi_thermo_set_eos: model must be 0 (ideal gas) or 1 (Peng-Robinson)");
+    Thermo& t = x.thermo;
+    if (model == 0) {   // clears: every thermo call launches the ideal-gas kernels again
+      t.eos = 0;
+      t.eos_a.clear(); t.eos_b.clear(); t.eos_w.clear();
+      return;
+    }
+    DFMI_CHECK(t.S > 0 && t.S == x.S, "dfmi_thermo_set_eos: call dfmi_thermo_set_coeffs first");
+    DFMI_CHECK(S == t.S, "dfmi_thermo_set_eos: num_species " + std::to_string(S) + " differs from the thermo table's " +
+                             std::to_string(t.S));
+    DFMI_CHECK(a && b && w, "dfmi_thermo_set_eos: null parameter array");
+    DFMI_CHECK(S <= 16, "dfmi_thermo_set_eos: the Peng-Robinson equation of state is not available with more than 16 species "
+                        "(the cooperative thermo kernel)");
+    auto finite = [](double v) { return v >= -1.79769313486231570e308 && v <= 1.79769313486231570e308; };
+    for (int i = 0; i < S; ++i) {
+      const std::string at = " of species " + std::to_string(i);
+      DFMI_CHECK(finite(a[i]) && finite(b[i]) && finite(w[i]), "dfmi_thermo_set_eos: a, b and acentric" + at + " must be finite");
+      DFMI_CHECK(a[i] >= 0.0, "dfmi_thermo_set_eos: a" + at + " must not be negative");
+      DFMI_CHECK(b[i] > 0.0, "dfmi_thermo_set_eos: b" + at + " must be positive");
+    }
+    ensure_eos_fields(x);
+    t.eos_a.assign(a, a + S); t.eos_b.assign(b, b + S); t.eos_w.assign(w, w + S);
+    thermo_eos_upload(x);
+    t.eos = 1;
+  });
+}
+
 int dfmi_thermo_load(dfmi_ctx* ctx, const char* path) {
   std::vector<double> all;
   int S = 0;
@@ -853,6 +892,7 @@ int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long cou
     const std::string n(name ? name : "");
     if (n == "delta" || n == "nut" || n == "boundary_nut") ensure_les_fields(x);
     if (ras_name(n)) ensure_ras_fields(x);
+    if (n == "rho_thermo" || n == "boundary_rho_thermo") ensure_eos_fields(x);
     if (tci_name(n)) {
       DFMI_CHECK(n == "tci_tc", "field '" + n + "' is formed by dfmi_combustion_correct and cannot be set");
       ensure_tci_fields(x);
@@ -884,6 +924,7 @@ int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, in
     const std::string n(name ? name : "");
     if (n == "delta" || n == "nut" || n == "boundary_nut") ensure_les_fields(ctx->x);
     if (ras_name(n)) ensure_ras_fields(ctx->x);
+    if (n == "rho_thermo" || n == "boundary_rho_thermo") ensure_eos_fields(ctx->x);
     if (n == "boundary_yPlus") ensure_wall_fields(ctx->x);
     if (tci_name(n)) ensure_tci_fields(ctx->x);
     copy_field(ctx->x, n, host, count, layout, false);
@@ -934,6 +975,15 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
       bool done = false;
       ~TimerReset() { if (!done) t.used = 0; }
     } treset{x.steptimer};
+    const bool eos = x.thermo.eos != 0;
+    if (eos) {   // the real-fluid step is the laminar, non-reacting one (include/dfmi.h dfmi_thermo_set_eos)
+      const char* why = "dfmi_time_step: with an equation of state set (dfmi_thermo_set_eos model 1) ";
+      DFMI_CHECK(x.chem.mode == 0, std::string(why) + "chem.mode != 0 is not available (real-fluid kinetics needs activity "
+                                                      "concentrations and the reactor's own density)");
+      DFMI_CHECK(!x.les.model, std::string(why) + "les.model != 0 is not available");
+      DFMI_CHECK(!x.ras.model, std::string(why) + "ras.model != 0 is not available");
+      DFMI_CHECK(!x.tci.model, std::string(why) + "tci.model != 0 is not available");
+    }
     if (x.steptimer.on && x.steptimer.used == 0) x.steptimer.mark(x.stream);
     x.dnn.prepared = false;         // never reuse a compaction of an earlier (failed) step
     if (x.les.model && !x.les.valid) { ensure_les_fields(x); turbulence_correct(x); }   // turbulence->validate() (dfLowMachFoam.C:207)
@@ -946,7 +996,22 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
     do_U_Y_E(x, early);             // UEqn, YEqn, EEqn (one rank: the chemistry and YEqn assembly beside the
                                     // UEqn, the EEqn assembly beside the Y solve)
     thermo_correct(x, false);       // correctThermo
-    for (int i = 0; i < n_corr; ++i) {   // pEqn_GPU.H
+    // Equation of state: thermo.rho_ (rho_thermo) is no longer psi p, so the corrector is the CPU solver's (pEqn.H:1-4, 8,
+    // 95): rho = thermo.rho(), psip0 = psi p, the p equation, thermo.rho_ += psi p - psip0. Its closing rhoEqn writes a
+    // rho that the next statement -- rho = thermo.rho() of the next corrector, or after the loop (dfLowMachFoam.C:517) --
+    // overwrites before anything in this laminar step reads it, as in the ideal-gas loop below.
+    for (int i = 0; eos && i < n_corr; ++i) {
+      if (i > 0) thermo_rho_from_psi(x);   // rho = rho_thermo (the first corrector's: correctThermo wrote both)
+      thermo_psip0(x);
+      if (i > 0 || !early) u_hbya(x);
+      const int keep = (int)x.opt("amg.reuse_steps");
+      x.amg.reuse_ok = i > 0 || (keep > 1 && x.amg.ready && x.amg.age > 0 && x.amg.age < keep);
+      if (i == 0) x.amg.age = x.amg.reuse_ok ? x.amg.age + 1 : 1;
+      do_p(x);
+      x.amg.reuse_ok = false;
+      thermo_correct_psip_rho(x);          // rho_thermo += psi p - psip0
+    }
+    for (int i = 0; !eos && i < n_corr; ++i) {   // pEqn_GPU.H
       // rho = psi p: the first corrector's is what correctThermo just wrote (the same product of the same p and psi,
       // halo included); psip0 = psi p feeds only correctPsipRho, skipped below (the field is not updated here)
       if (i > 0) thermo_rho_from_psi(x);
@@ -1387,6 +1452,8 @@ int dfmi_zero_d_step(dfmi_ctx* ctx, double dt, int n_steps) {
     Ctx& x = ctx->x;
     require_ready(x);
     DFMI_CHECK(dt > 0 && n_steps >= 1, "0D step: dt and n_steps must be positive");
+    DFMI_CHECK(!x.thermo.eos, "dfmi_zero_d_step is not available with an equation of state set (dfmi_thermo_set_eos model 1): "
+                              "the reactor's chemistry is the ideal-gas one");
     x.dnn.prepared = false;
     // no host synchronisation inside the loop: the steps' launches queue back to back (one round trip per step
     // bounded config 1 at ~0.1 ms/step), the chemistry's failure counter sums over the batch and is read once

@@ -99,6 +99,11 @@ struct Thermo {
   // binary-diffusion table, its unique pairs in rotation order [d - 1][i][6] = coefficients of the pair
   // (i, (i + d) mod S), d = 1 .. S / 2, padded to 6 (three 16-B loads)
   DevBuf<double> dvcP, dbdR;
+  // equation of state (dfmi_thermo_set_eos): 0 ideal gas, 1 Peng-Robinson with the species' a [Pa m^6 / kmol^2],
+  // b [m^3 / kmol] and acentric factor; on the device sqrt(a_i), kappa_i, 1 / sqrt(Tc_i) and b_i (thermo_eos_upload)
+  int eos = 0;
+  std::vector<double> eos_a, eos_b, eos_w;
+  DevBuf<double> dsqa, dkap, drsTc, deb;
 };
 
 struct Halo;   // RCCL processor-patch exchange (halo.hip)
@@ -638,6 +643,7 @@ void thermo_psip0(Ctx& x);
 void thermo_correct_psip_rho(Ctx& x);
 // thermo.hip
 void thermo_upload(Ctx& x);
+void thermo_eos_upload(Ctx& x);   // the Peng-Robinson species constants from Thermo::eos_a / eos_b / eos_w
 std::vector<double> heat_of_formation_per_mass(int S, const double* W, const double* nasa);   // hc_i (Qdot weights)
 void thermo_correct(Ctx& x, bool from_T);
 // boundary_heGradient on gradientEnergy slots of he (0 elsewhere)

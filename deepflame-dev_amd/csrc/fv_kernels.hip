@@ -3522,6 +3522,13 @@ double hbm_copy_gbs(Ctx& x, size_t bytes, int reps) {
 }
 
 void thermo_rho_from_psi(Ctx& x) {   // dfThermo::updateRho (dfThermo.cu:673-679)
+  if (x.thermo.eos) {   // rho = thermo.rho(), which with an equation of state is rho_thermo and not psi p
+    DFMI_HIP(hipMemcpyAsync(x.f("rho"), x.f("rho_thermo"), sizeof(double) * x.C, hipMemcpyDeviceToDevice, x.stream));
+    if (x.B > 0)
+      DFMI_HIP(hipMemcpyAsync(x.f("boundary_rho"), x.f("boundary_rho_thermo"), sizeof(double) * x.B, hipMemcpyDeviceToDevice,
+                              x.stream));
+    return;
+  }
   LAUNCH(k_mul, x.C, (long)x.C, x.f("p"), x.f("psi"), x.f("rho"));
   LAUNCH(k_mul, x.B, (long)x.B, x.f("boundary_p"), x.f("boundary_psi"), x.f("boundary_rho"));
 }
@@ -3530,6 +3537,11 @@ void thermo_psip0(Ctx& x) {          // dfThermo::psip0 (:681-686)
   LAUNCH(k_mul, x.B, (long)x.B, x.f("boundary_psi"), x.f("boundary_p"), x.f("boundary_psip0"));
 }
 void thermo_correct_psip_rho(Ctx& x) {   // dfThermo::correctPsipRho (:688-695)
+  if (x.thermo.eos) {   // thermo.rho_ += psi p - psip0
+    LAUNCH(k_add_psip, x.C, (long)x.C, x.f("p"), x.f("psi"), x.f("psip0"), x.f("rho_thermo"));
+    LAUNCH(k_add_psip, x.B, (long)x.B, x.f("boundary_p"), x.f("boundary_psi"), x.f("boundary_psip0"), x.f("boundary_rho_thermo"));
+    return;
+  }
   LAUNCH(k_add_psip, x.C, (long)x.C, x.f("p"), x.f("psi"), x.f("psip0"), x.f("rho"));
   LAUNCH(k_add_psip, x.B, (long)x.B, x.f("boundary_p"), x.f("boundary_psi"), x.f("boundary_psip0"), x.f("boundary_rho"));
 }

@@ -9,6 +9,8 @@
 // per-cell species arrays stay in VGPRs (runtime-indexed arrays would go to scratch); the coefficient
 // tables are wave-uniform reads (scalar cache). HBM traffic per cell: read Y[S], he, p, T;
 // write T, he, psi, rho, mu, alpha, rhoD[S], hai[S].
+// With a Peng-Robinson equation of state set (dfmi_thermo_set_eos) the pair k_thermo_cells_pr / k_thermo_slots_pr runs
+// instead: the same point with rho from the cubic, T(h) to rounding and psi as a constant-enthalpy difference quotient.
 #include "dfmi_ctx.h"
 #include <cstdlib>
 #include <cmath>
@@ -66,16 +68,129 @@ __device__ __forceinline__ void hcp_mix(const TC& t, double T, const double* ryw
   }
 }
 
+// ---------------------------------------------------------------- Peng-Robinson (dfmi_thermo_set_eos)
+// One fluid with geometric-mean cross terms: (a alpha) = (sum_i X_i sqrt(a_i) |s_i|)^2, s_i = 1 + kappa_i (1 - sqrt(T / Tc_i)),
+// b = sum_i X_i b_i, so the mixing sums are O(S) and the species constants are wave-uniform reads. tests/realfluid_reference.py
+// states the same operations in NumPy (float64 and long double); the tolerances of the kernels come from those two.
+struct PR { const double *sqa, *kap, *rsTc, *b; };   // sqrt(a_i), kappa_i, 1 / sqrt(Tc_i) (0 where a_i = 0), b_i
+constexpr double PR_SQ2 = 1.4142135623730951, PR_DX = 1e-4, PR_EPS4 = 4.0 * 2.220446049250313e-16;
+constexpr double PR_2PI3 = 2.0943951023931957, PR_4PI3 = 4.1887902047863914;
+
+// Newton steps on Z^3 + a2 Z^2 + a1 Z + a0 from a closed-form root until the step is at rounding (or has stopped
+// shrinking below 1e-9 |Z|)
+__device__ __forceinline__ double pr_polish(double z, double a2, double a1, double a0) {
+  double prev = INFINITY;
+  for (int n = 0; n < 30; ++n) {
+    const double f = ((z + a2) * z + a1) * z + a0, fp = (3.0 * z + 2.0 * a2) * z + a1;
+    if (fp == 0.0) break;
+    const double dz = f / fp, a = fabs(dz);
+    if (a >= prev && prev <= 1e-9 * fabs(z)) break;
+    z -= dz;
+    prev = a;
+    if (a <= PR_EPS4 * fabs(z)) break;
+  }
+  return z;
+}
+__device__ __forceinline__ double pr_lnphi(double z, double A, double B) {
+  return z - 1.0 - log(z - B) - A / (2.0 * PR_SQ2 * B) * log1p(2.0 * PR_SQ2 * B / (z + (1.0 - PR_SQ2) * B));
+}
+// the compressibility factor: the cubic's largest root, or its smallest when that lies above B and has the lower ln phi
+__device__ __forceinline__ double pr_cubic(double A, double B) {
+  const double a2 = -(1.0 - B), a1 = A - 3.0 * B * B - 2.0 * B, a0 = -(A * B - B * B - B * B * B);
+  const double sh = -a2 / 3.0;
+  const double pp = a1 - a2 * a2 / 3.0;
+  const double qq = 2.0 * a2 * a2 * a2 / 27.0 - a2 * a1 / 3.0 + a0;
+  const double D = qq * qq / 4.0 + pp * pp * pp / 27.0;
+  if (D > 0.0) {   // one real root (Cardano, the root of larger magnitude first)
+    const double u = (qq > 0.0 ? -1.0 : 1.0) * cbrt(fabs(qq) / 2.0 + sqrt(D));
+    const double z1 = (u == 0.0 ? 0.0 : u - pp / (3.0 * u)) + sh;
+    return pr_polish(z1, a2, a1, a0);
+  }
+  const double r = 2.0 * sqrt(fmax(-pp / 3.0, 0.0)), den = pp * r;
+  const double arg = den == 0.0 ? 0.0 : fmin(fmax(3.0 * qq / den, -1.0), 1.0);
+  const double th = acos(arg) / 3.0;
+  const double zmax = pr_polish(r * cos(th) + sh, a2, a1, a0);
+  const double zmin = pr_polish(r * cos(th - PR_4PI3) + sh, a2, a1, a0);
+  if (zmin > B && pr_lnphi(zmin, A, B) < pr_lnphi(zmax, A, B)) return zmin;
+  return zmax;
+}
+
+// rho, h, cp of the mixture at (T, p): X mole fractions, ryw[i] = R Y_i / W_i, bm = sum X_i b_i
+template <int S>
+__device__ __forceinline__ void pr_state(const TC& t, const PR& e, const double* X, const double* ryw, double Wm, double bm,
+                                         double T, double p, double& rho, double& h, double& cp) {
+#pragma clang fp contract(fast)
+  double h_ig, cp_ig;
+  hcp_mix<S>(t, T, ryw, h_ig, cp_ig);
+  const double sT = sqrt(T);
+  double A0 = 0., Q = 0.;
+#pragma unroll
+  for (int i = 0; i < S; ++i) {
+    const double kap = e.kap[i], rs = e.rsTc[i];
+    const double s = 1.0 + kap * (1.0 - sT * rs), c0 = X[i] * e.sqa[i];
+    A0 += c0 * fabs(s);
+    Q += (s < 0.0 ? -c0 : c0) * kap * rs;
+  }
+  const double A1 = -Q / (2.0 * sT), A2 = Q / (4.0 * T * sT);
+  const double aal = A0 * A0, d1 = 2.0 * A0 * A1, d2 = 2.0 * (A1 * A1 + A0 * A2);
+  const double RT = R_GAS * T;
+  const double A = aal * p / (RT * RT), B = bm * p / RT;
+  const double Z = pr_cubic(A, B);
+  const double v = Z * RT / p;
+  const double L = log1p(2.0 * PR_SQ2 * B / (Z + (1.0 - PR_SQ2) * B));
+  const double k = 1.0 / (2.0 * PR_SQ2 * bm);
+  h = h_ig + (RT * (Z - 1.0) + (T * d1 - aal) * k * L) / Wm;
+  const double vb = v - bm, dn = v * v + 2.0 * bm * v - bm * bm;
+  const double pT = R_GAS / vb - d1 / dn;
+  const double pv = -RT / (vb * vb) + aal * (2.0 * v + 2.0 * bm) / (dn * dn);
+  cp = cp_ig + (-R_GAS + T * d2 * k * L - T * pT * pT / pv) / Wm;
+  rho = p * Wm / (Z * RT);
+}
+
+// T (from he unless fixT), he, cp, rho at p, and psi = (rho(he, p) - rho(he, p (1 - dx))) / (dx p): two constant-enthalpy
+// Newton solves, dT = (h - he) / cp, the second started at the first one's T. Each is carried to rounding: it stops when
+// |dT| <= 4 2^-52 T, when the step has stopped shrinking below 1e-9 T, or after 40 steps.
+template <int S>
+__device__ __forceinline__ void pr_solve(const TC& t, const PR& e, bool fixT, const double* X, const double* ryw, double Wm,
+                                         double& T, double& he, double p, double& cpm, double& psi, double& rho) {
+  double bm = 0.;
+#pragma unroll
+  for (int i = 0; i < S; ++i) bm += X[i] * e.b[i];
+  double tt = T, rho1 = 0.;
+  for (int pass = 0; pass < 2; ++pass) {
+    const double pp = pass ? p * (1.0 - PR_DX) : p;
+    bool last = fixT && pass == 0;   // evaluate once at the given T
+    double prev = INFINITY, r, h, cp;
+    for (int n = 0;; ++n) {
+      pr_state<S>(t, e, X, ryw, Wm, bm, tt, pp, r, h, cp);
+      if (last || n >= 40) break;
+      const double dT = (h - he) / cp, a = fabs(dT);
+      if (a >= prev && prev <= 1e-9 * tt) break;
+      tt -= dT;
+      prev = a;
+      if (a <= PR_EPS4 * fabs(tt)) last = true;   // one more evaluation, at the final T
+    }
+    if (pass == 0) {
+      if (fixT) he = h;
+      T = tt; cpm = cp; rho1 = r;
+    } else {
+      psi = (rho1 - r) / (PR_DX * p);
+    }
+  }
+  rho = rho1;
+}
+
 // state (T or he), p, Y -> T, he, psi, rho, mu, alpha, rhoD[S], hai[S]; mirrors oracle thermo_point
 // (same formulas; divisions hoisted out of the O(S^2) loops -- reciprocals of the species
 // viscosities, one reciprocal per binary-diffusion pair when the fit table is symmetric -- and the
 // per-species divisions as products with 1/W, T powers shared per temperature (tpow) and Newton-refined
 // reciprocals (rcp_nr), so the result agrees with the sequential evaluation to rounding, not bitwise;
 // the Newton step and its stopping test keep their divisions, so the iteration count is the oracle's)
-template <int S>
+// EOS: the Peng-Robinson state (T, he, cp, psi, rho from pr_solve) in place of the ideal-gas one; the transport is shared
+template <int S, bool EOS = false>
 __device__ __forceinline__ void thermo_point(const TC& t, bool fixT, double& T, double& he, double p, const double* y,
                                              double& psi, double& rho, double& mu, double& alpha, double* rhoD,
-                                             double* hai) {
+                                             double* hai, const PR* eos = nullptr) {
   // products contracted into FMAs (the result agrees with the oracle to rounding either way): ~30 % fewer
   // VALU instructions in the O(S^2) rows of this FP64-issue-bound kernel
 #pragma clang fp contract(fast)
@@ -88,7 +203,9 @@ __device__ __forceinline__ void thermo_point(const TC& t, bool fixT, double& T, 
 #pragma unroll
   for (int i = 0; i < S; ++i) { X[i] = y[i] * t.rW[i] * rsum; Wm += X[i] * t.W[i]; }
   double cpm = 0.;
-  if (fixT) {
+  if constexpr (EOS) {
+    pr_solve<S>(t, *eos, fixT, X, ryw, Wm, T, he, p, cpm, psi, rho);
+  } else if (fixT) {
     hcp_mix<S>(t, T, ryw, he, cpm);
   } else {
     double tt = T;
@@ -106,8 +223,10 @@ __device__ __forceinline__ void thermo_point(const TC& t, bool fixT, double& T, 
   const double lnT = log(T);
   double poly[5];
   poly[0] = 1.0; poly[1] = lnT; poly[2] = poly[1] * poly[1]; poly[3] = poly[1] * poly[2]; poly[4] = poly[2] * poly[2];
-  psi = Wm / (R_GAS * T);
-  rho = p * psi;
+  if constexpr (!EOS) {
+    psi = Wm / (R_GAS * T);
+    rho = p * psi;
+  }
   // Wilke mixture viscosity
   double sv[S], rsv[S], xs[S];
 #pragma unroll
@@ -247,6 +366,55 @@ __global__ void __launch_bounds__(256) k_thermo_slots(MeshView m, TC t, const in
   double Tb = T[b], hb = he[b], ps, r, mm, a;
   thermo_point<S>(t, fromT != 0 || bc_fixes_value(ty), Tb, hb, p[b], y, ps, r, mm, a, rd, ha);
   thermo_store<S>(b, B, T, he, psi, rho, mu, alpha, rhoD, hai, Tb, hb, ps, r, mm, a, rd, ha);
+}
+
+// The Peng-Robinson forms of the two kernels (one cell or slot per lane, species arrays in VGPRs): the same stores plus
+// rho_thermo (OpenFOAM's thermo.rho_, which dfmi_time_step advances by psi p - psip0 between correctThermo calls)
+template <int S>
+__global__ void __launch_bounds__(256) k_thermo_cells_pr(int n, TC t, PR e, int fixT, double* __restrict__ T, double* __restrict__ he,
+    const double* __restrict__ p, const double* __restrict__ Y, double* __restrict__ psi, double* __restrict__ rho,
+    double* __restrict__ rho_th, double* __restrict__ mu, double* __restrict__ alpha, double* __restrict__ rhoD,
+    double* __restrict__ hai) {
+  const int c = xcd_block() * blockDim.x + threadIdx.x;
+  if (c >= n) return;
+  double y[S], rd[S], ha[S];
+#pragma unroll
+  for (int i = 0; i < S; ++i) y[i] = Y[(long)i * n + c];
+  double Tc = T[c], hc = he[c], ps, r, m, a;
+  thermo_point<S, true>(t, fixT != 0, Tc, hc, p[c], y, ps, r, m, a, rd, ha, &e);
+  thermo_store<S>(c, n, T, he, psi, rho, mu, alpha, rhoD, hai, Tc, hc, ps, r, m, a, rd, ha);
+  rho_th[c] = r;
+}
+
+template <int S>
+__global__ void __launch_bounds__(256) k_thermo_slots_pr(MeshView m, TC t, PR e, const int8_t* __restrict__ tyT, int fromT,
+    const double* __restrict__ cT, const double* __restrict__ che, const double* __restrict__ cpsi,
+    const double* __restrict__ crho, const double* __restrict__ cmu, const double* __restrict__ calpha,
+    const double* __restrict__ crhoD, const double* __restrict__ chai, double* __restrict__ T, double* __restrict__ he,
+    const double* __restrict__ p, const double* __restrict__ Y, double* __restrict__ psi, double* __restrict__ rho,
+    double* __restrict__ rho_th, double* __restrict__ mu, double* __restrict__ alpha, double* __restrict__ rhoD,
+    double* __restrict__ hai) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  const int B = m.B;
+  if (b >= B) return;
+  const int ty = tyT[b];
+  if (ty == EMPTY) return;
+  if (bc_proc(ty) && !m.sprim[b]) {
+    const int c = m.bfc[b];
+    const long C = m.C;
+    T[b] = cT[c]; he[b] = che[c]; psi[b] = cpsi[c]; rho[b] = crho[c]; rho_th[b] = crho[c];
+    mu[b] = cmu[c]; alpha[b] = calpha[c];
+#pragma unroll
+    for (int i = 0; i < S; ++i) { rhoD[(long)i * B + b] = crhoD[i * C + c]; hai[(long)i * B + b] = chai[i * C + c]; }
+    return;
+  }
+  double y[S], rd[S], ha[S];
+#pragma unroll
+  for (int i = 0; i < S; ++i) y[i] = Y[(long)i * B + b];
+  double Tb = T[b], hb = he[b], ps, r, mm, a;
+  thermo_point<S, true>(t, fromT != 0 || bc_fixes_value(ty), Tb, hb, p[b], y, ps, r, mm, a, rd, ha, &e);
+  thermo_store<S>(b, B, T, he, psi, rho, mu, alpha, rhoD, hai, Tb, hb, ps, r, mm, a, rd, ha);
+  rho_th[b] = r;
 }
 
 // mixture enthalpy summed exactly as calculate_enthalpy_device_kernel (dfThermo.cu:257-274) and the
@@ -780,6 +948,25 @@ void thermo_upload(Ctx& x) {
   DFMI_HIP(hipStreamSynchronize(x.stream));   // the staging vectors above go out of scope
 }
 
+// kappa_i by the acentric factor's branch, Tc_i = (Omega_b / Omega_a) a_i / (b_i R); a species without attraction
+// (a_i = 0) has no critical temperature and contributes nothing: 1 / sqrt(Tc_i) := 0
+void thermo_eos_upload(Ctx& x) {
+  Thermo& t = x.thermo;
+  const int S = t.S;
+  constexpr double OMEGA_A = 0.45723552892138218, OMEGA_B = 0.0777960739038885;
+  std::vector<double> sqa(S), kap(S), rs(S);
+  for (int i = 0; i < S; ++i) {
+    const double w = t.eos_w[i];
+    kap[i] = w <= 0.491 ? 0.37464 + 1.54226 * w - 0.26992 * w * w
+                        : 0.379642 + 1.487503 * w - 0.164423 * w * w + 0.016666 * w * w * w;
+    const double Tc = (OMEGA_B / OMEGA_A) * t.eos_a[i] / (t.eos_b[i] * R_GAS);
+    sqa[i] = std::sqrt(t.eos_a[i]);
+    rs[i] = Tc > 0 ? 1.0 / std::sqrt(Tc) : 0.0;
+  }
+  t.dsqa.upload(sqa, x.stream); t.dkap.upload(kap, x.stream); t.drsTc.upload(rs, x.stream); t.deb.upload(t.eos_b, x.stream);
+  DFMI_HIP(hipStreamSynchronize(x.stream));   // the staging vectors above go out of scope
+}
+
 void thermo_energy_gradient(Ctx& x) {
   Thermo& th = x.thermo;
   DFMI_CHECK(th.S == x.S, "thermo coefficients not set or species count mismatch");
@@ -819,6 +1006,39 @@ void thermo_correct(Ctx& x, bool from_T) {
   TC t{th.dW, th.drW, th.dnasa, th.dvisc, th.dcond, th.dbdiff, th.dvc1, th.dvc2, sym, th.dnasaT, th.dbdiffT, th.dvc1T, th.dvc2T,
        th.dvcP, sym && th.dbdR.n ? th.dbdR.p : nullptr};
   MeshView m = x.view();
+  if (th.eos == 1) {   // Peng-Robinson (dfmi_thermo_set_eos): register-resident species counts only
+    DFMI_CHECK(!species_generic(x), "thermo: the Peng-Robinson equation of state is not available with fv.species_generic "
+                                    "or more than 16 species (the cooperative kernel)");
+    PR e{th.dsqa, th.dkap, th.drsTc, th.deb};
+#define CALL_PR(NS)                                                                                                   \
+  do {                                                                                                                \
+    if (x.C > 0) { KScope _ks(x, "k_thermo_cells_pr");                                                                \
+      hipLaunchKernelGGL(k_thermo_cells_pr<NS>, dim3(blocks_for(x.C, 256)), dim3(256), 0, x.stream, x.C, t, e,        \
+                         (int)from_T, x.f("T"), x.f("he"), x.f("p"), x.f("Y"), x.f("psi"), x.f("rho"),                \
+                         x.f("rho_thermo"), x.f("mu"), x.f("alpha"), x.f("rhoD"), x.f("hai")); }                      \
+    DFMI_HIP(hipGetLastError());                                                                                      \
+    if (x.B > 0) hipLaunchKernelGGL(k_thermo_slots_pr<NS>, dim3(blocks_for(x.B, 256)), dim3(256), 0, x.stream, m, t,  \
+                       e, x.st("T"), (int)from_T, x.f("T"), x.f("he"), x.f("psi"), x.f("rho"), x.f("mu"),             \
+                       x.f("alpha"), x.f("rhoD"), x.f("hai"), x.f("boundary_T"), x.f("boundary_he"),                  \
+                       x.f("boundary_p"), x.f("boundary_Y"), x.f("boundary_psi"), x.f("boundary_rho"),                \
+                       x.f("boundary_rho_thermo"), x.f("boundary_mu"), x.f("boundary_alpha"), x.f("boundary_rhoD"),   \
+                       x.f("boundary_hai"));                                                                          \
+    DFMI_HIP(hipGetLastError());                                                                                      \
+  } while (0)
+    switch (x.S) {
+      case 2: CALL_PR(2); break; case 3: CALL_PR(3); break; case 4: CALL_PR(4); break; case 5: CALL_PR(5); break;
+      case 6: CALL_PR(6); break; case 7: CALL_PR(7); break; case 8: CALL_PR(8); break; case 9: CALL_PR(9); break;
+      case 10: CALL_PR(10); break; case 11: CALL_PR(11); break; case 12: CALL_PR(12); break; case 13: CALL_PR(13); break;
+      case 14: CALL_PR(14); break; case 15: CALL_PR(15); break; case 16: CALL_PR(16); break;
+      default: throw Error("dfmi: thermo species count " + std::to_string(x.S) + " not supported");
+    }
+#undef CALL_PR
+    std::vector<const char*> names;
+    if (from_T) names.push_back("he");
+    for (const char* f : {"T", "psi", "rho", "rho_thermo", "mu", "alpha", "rhoD", "hai"}) names.push_back(f);
+    halo_fields(x, names);
+    return;
+  }
 #define CALL(NS)                                                                                                  \
   do {                                                                                                            \
     if (x.C > 0) { KScope _ks(x, "k_thermo_cells");                                                               \

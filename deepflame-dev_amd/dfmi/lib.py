@@ -52,6 +52,7 @@ SIGNATURES = {
     "dfmi_set_scheme": [_P, C.c_char_p, C.c_char_p],
     "dfmi_thermo_set_coeffs": [_P, C.c_int, _DP, _DP, _DP, _DP, _DP],
     "dfmi_thermo_load": [_P, C.c_char_p],
+    "dfmi_thermo_set_eos": [_P, C.c_int, C.c_int, _DP, _DP, _DP],
     "dfmi_set_field": [_P, C.c_char_p, _DP, C.c_long, C.c_int],
     "dfmi_get_field": [_P, C.c_char_p, _DP, C.c_long, C.c_int],
     "dfmi_pre_time_step": [_P], "dfmi_rho_process": [_P], "dfmi_U_process": [_P], "dfmi_Y_process": [_P],
@@ -287,6 +288,15 @@ class Context:
     def thermo_set_coeffs(self, t):
         arrs = [_f64(x) for x in (t.W, t.nasa, t.visc, t.cond, t.bdiff)]
         self._call("dfmi_thermo_set_coeffs", self.h, t.S, *[_dp(a) for a in arrs])
+
+    def thermo_set_eos(self, model, a=None, b=None, acentric=None):
+        """equation of state (include/dfmi.h dfmi_thermo_set_eos): model 0 clears, 1 is Peng-Robinson with the species'
+        a [Pa m^6 / kmol^2], b [m^3 / kmol] and acentric factor; after thermo_set_coeffs"""
+        if int(model) == 0 and a is None:
+            self._call("dfmi_thermo_set_eos", self.h, 0, 0, None, None, None)
+            return
+        arrs = [_f64(x) for x in (a, b, acentric)]
+        self._call("dfmi_thermo_set_eos", self.h, int(model), int(arrs[0].size), *[_dp(x) for x in arrs])
 
     # --- fields
     def set_field(self, name, arr, layout=0):

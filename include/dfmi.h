@@ -175,6 +175,20 @@ int dfmi_thermo_set_coeffs(dfmi_ctx* ctx, int num_species, const double* W, cons
                            const double* visc, const double* cond, const double* bdiff);
 /* read the reference's binary thermo_<mech>.txt */
 int dfmi_thermo_load(dfmi_ctx* ctx, const char* thermo_coeff_file);
+/* Equation of state. model 0: ideal gas (clears; the arrays are not read), 1: Peng-Robinson with the species'
+ * a [Pa m^6 / kmol^2], b [m^3 / kmol] and acentric factor (Cantera's units), geometric-mean cross terms, no binary overrides.
+ * Call it after dfmi_thermo_set_coeffs with the same num_species. Refused by name: a model other than 0 or 1, a species
+ * count that differs, a value that is not finite, a < 0, b <= 0, and model 1 with more than 16 species.
+ * With model 1 dfmi_thermo_correct / dfmi_thermo_update_energy take rho from the cubic (the root of lowest fugacity), T from
+ * he by Newton steps carried to rounding, psi = (rho(he, p) - rho(he, p (1 - 1e-4))) / (1e-4 p) at constant enthalpy
+ * (CanteraMixture.H:116-149), alpha = lambda / cp with the real cp and rhoD_i with the real rho; mu, lambda and hai_i keep
+ * the ideal forms. They also write the field rho_thermo (OpenFOAM's thermo.rho_, no longer psi p), and dfmi_time_step follows
+ * the CPU solver's corrector (pEqn.H:1-4, 8, 95; dfLowMachFoam.C:517): rho = rho_thermo, psip0 = psi p, the p equation,
+ * rho_thermo += psi p - psip0, the rhoEqn; after the loop rho = rho_thermo. dfmi_thermo_update_rho copies rho_thermo to rho,
+ * dfmi_thermo_psip0 is unchanged and dfmi_thermo_correct_psip_rho acts on rho_thermo. With model 0 every launch is the
+ * ideal-gas one. Refused by name with model 1: option fv.species_generic (at the thermo call); at dfmi_time_step chemistry
+ * mode != 0 and les.model / ras.model / tci.model != 0; dfmi_zero_d_step. */
+int dfmi_thermo_set_eos(dfmi_ctx* ctx, int model, int num_species, const double* a, const double* b, const double* acentric);
 
 /* ---- fields (initNonConstantFields*, getFieldPointer dfMatrixDataBase.cu:521-539) ---------- */
 /* names: cells  rho rho_old p p_old he T K K_old psi mu alpha dpdt rAU diffAlphaD psip0
@@ -186,7 +200,8 @@ int dfmi_thermo_load(dfmi_ctx* ctx, const char* thermo_coeff_file);
  *        LES: delta (cells; positive), nut (cells; get only), boundary_nut (set: the fixedValue / calculated slots).
  *        RAS: k epsilon (cells), boundary_{k,epsilon}, boundary_{k,epsilon}_ref; get only: G divU k_prebound epsilon_prebound,
  *        boundary_yPlus (the nutkWallFunction slots' yPlus, zero elsewhere).
- *        Combustion closure: tci_tc (cells); get only: tci_kappa tci_tmix tci_tauStar Qdot_eff (cells), RR_eff (species). */
+ *        Combustion closure: tci_tc (cells); get only: tci_kappa tci_tmix tci_tauStar Qdot_eff (cells), RR_eff (species).
+ *        Equation of state: rho_thermo, boundary_rho_thermo (thermo.rho_; allocated at the first dfmi_thermo_set_eos or use). */
 int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long count, int layout);
 int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, int layout);
 
