@@ -107,6 +107,10 @@ struct Ctx {
                                        {"tci.oxidizer", -1}, {"tci.CO2", -1}, {"tci.H2", -1}, {"tci.version", 2005},
                                        {"tci.C1", 0.05774}, {"tci.C2", 0.5}, {"tci.Cgamma", 2.1377}, {"tci.Ctau", 0.4083},
                                        {"tci.exp1", 0}, {"tci.exp2", 0}, {"tci.bad_tauStar", 0}};
+  // flareFGM (options fgm.*): the keys and defaults of the HIP library, accepted and kept; fgm.model = 1 is refused by name
+  std::map<std::string, double> fgm = {{"fgm.model", 0}, {"fgm.combustion", 0}, {"fgm.solveEnthalpy", 0}, {"fgm.flameletT", 0},
+                                       {"fgm.Sct", 0.7}, {"fgm.Sc", 1.0}, {"fgm.incompPref", -10.0}, {"fgm.TMin", 200.0},
+                                       {"fgm.TMax", 5000.0}};
   struct Les { int model = 0; double Ck = 0.094, Ce = 1.048, Cw = 0.325, Prt = 1.0, Sct = 1.0; bool valid = false, have_delta = false; } les;
   bool step_courant = false;   // option step.courant: accepted for the callers that set it; the number is always computed on demand
   bool have_sizes = false, have_topo = false, have_geom = false, have_bgeom = false;
@@ -1331,6 +1335,18 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
       it->second = value;
       return;
     }
+    if (ctx && key && std::string(key).rfind("fgm.", 0) == 0) {   // the keys of the HIP library; the model itself is its alone
+      const std::string k(key);
+      auto it = ctx->x.fgm.find(k);
+      CHECK(it != ctx->x.fgm.end(), "unknown option '" + k + "'");
+      if (k == "fgm.model" || k == "fgm.combustion" || k == "fgm.solveEnthalpy" || k == "fgm.flameletT") {
+        CHECK(value == 0.0 || value == 1.0, k + " must be 0 or 1");
+        CHECK(k != "fgm.model" || value == 0.0, "fgm.model = 1: CPU-A does not implement the flareFGM combustion model (the HIP library)");
+      } else if (k == "fgm.incompPref") CHECK(value >= -1.79769313486231570e308 && value <= 1.79769313486231570e308, "fgm.incompPref must be finite");
+      else CHECK(value > 0 && value <= 1.79769313486231570e308, k + " must be positive and finite");
+      it->second = value;
+      return;
+    }
     if (ctx && key && std::string(key).rfind("ras.", 0) == 0) {   // the keys of the HIP library; the model itself is its alone
       const std::string k(key);
       auto it = ctx->x.ras.find(k);
@@ -1361,6 +1377,12 @@ int dfmi_get_option(dfmi_ctx* ctx, const char* key, double* value) {
     if (ctx && key && value && std::string(key).rfind("tci.", 0) == 0) {
       auto it = ctx->x.tci.find(key);
       CHECK(it != ctx->x.tci.end(), std::string("unknown option '") + key + "'");
+      *value = it->second;
+      return;
+    }
+    if (ctx && key && value && std::string(key).rfind("fgm.", 0) == 0) {
+      auto it = ctx->x.fgm.find(key);
+      CHECK(it != ctx->x.fgm.end(), std::string("unknown option '") + key + "'");
       *value = it->second;
       return;
     }
@@ -1480,6 +1502,26 @@ int dfmi_chem_set_options(dfmi_ctx* ctx, int mode, double rtol, double atol, dou
 }
 int dfmi_chem_solve(dfmi_ctx* ctx, double dt) {
   return guard([&] { require_ready(ctx->x); CHECK(dt > 0, "dt must be positive"); chem_solve(ctx->x, dt, "rho"); });
+}
+// flareFGM: exported for callers that probe the ABI; the model is the HIP library's alone (fgm.model = 1 is refused above)
+int dfmi_fgm_set_table(dfmi_ctx* ctx, const int*, const double*, double, double, const double*, const double*, const double*,
+                       const double*, const int*, const int*) {
+  return guard([&] {
+    CHECK(ctx, "null context");
+    throw Error("dfmi_fgm_set_table: CPU-A does not implement the flareFGM combustion model (the HIP library)");
+  });
+}
+int dfmi_fgm_retrieve(dfmi_ctx* ctx) {
+  return guard([&] {
+    CHECK(ctx, "null context");
+    throw Error("dfmi_fgm_retrieve: CPU-A does not implement the flareFGM combustion model (the HIP library)");
+  });
+}
+int dfmi_fgm_correct(dfmi_ctx* ctx) {
+  return guard([&] {
+    CHECK(ctx, "null context");
+    throw Error("dfmi_fgm_correct: CPU-A does not implement the flareFGM combustion model (the HIP library)");
+  });
 }
 // combustion->correct(): tci.model is always 0 here, so this is the solve
 int dfmi_combustion_correct(dfmi_ctx* ctx, double dt) {

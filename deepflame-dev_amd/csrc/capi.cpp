@@ -140,6 +140,51 @@ void ensure_eos_fields(Ctx& x) {
   alloc_field(x, "rho_thermo", x.C, 1, false);
   alloc_field(x, "boundary_rho_thermo", x.B, 1, true);
 }
+// flareFGM (options fgm.*): the six transported scalars, what the retrieval writes beside the thermo fields,
+// the transport's diffusivity and source, and the thermo's own density (rho_thermo). Allocated when fgm.model is first
+// non-zero, a table is set, or one of these fields or their patch types is first touched: nothing in an FGM-free context.
+// Wt, Cp and Hf start at the reference's initial values (baseFGM.C:62, 75, 125); omega_Yi has one component per source
+// species of the table (one before a table is set).
+const char* const kFgmFields[] = {"Z", "Zvar", "c", "cvar", "Zcvar", "Ha", "chi_Z", "chi_Zc", "chi_c", "omega_c", "cOmega_c",
+                                  "ZOmega_c", "Ha_s", "c_s", "Zvar_s", "cvar_s", "Zcvar_s", "Wt", "Cp", "Hf", "fgm_D"};
+bool fgm_name(const std::string& n) {
+  const std::string b = n.rfind("boundary_", 0) == 0 ? n.substr(9) : n;
+  for (const char* s : kFgmFields) if (b == s) return true;
+  return b == "omega_Yi" || n == "fgm_Su";
+}
+void fill_field(Ctx& x, const std::string& name, double v) {
+  Field& f = x.fields.at(name);
+  std::vector<double> h((size_t)f.n * f.ncomp, v);
+  DFMI_HIP(hipMemcpyAsync(f.buf.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, x.stream));
+  DFMI_HIP(hipStreamSynchronize(x.stream));
+}
+void ensure_fgm_fields(Ctx& x) {
+  const int no = std::max(x.fgm.NYomega, 1);
+  if (x.fields.count("Zcvar")) {
+    if (x.fields.at("omega_Yi").ncomp != no) {   // a table with another NYomega
+      alloc_field(x, "omega_Yi", x.C, no, false);
+      alloc_field(x, "boundary_omega_Yi", x.B, no, true);
+    }
+    return;
+  }
+  DFMI_CHECK(x.have_bgeom, "call dfmi_init_constant_fields_boundary first");
+  ensure_ras_fields(x);
+  ensure_eos_fields(x);
+  for (const char* n : kFgmFields) {
+    alloc_field(x, n, x.C, 1, false);
+    alloc_field(x, std::string("boundary_") + n, x.B, 1, true);
+  }
+  alloc_field(x, "omega_Yi", x.C, no, false);
+  alloc_field(x, "boundary_omega_Yi", x.B, no, true);
+  alloc_field(x, "fgm_Su", x.C, 1, false);
+  alloc_field(x, "fgm_Sp", x.C, 1, false);   // stays zero: no implicit source in any of the six equations
+  for (const char* pre : {"", "boundary_"}) {
+    fill_field(x, std::string(pre) + "Wt", 28.96);
+    fill_field(x, std::string(pre) + "Cp", 1010.1);
+    fill_field(x, std::string(pre) + "Hf", 1907.0);
+  }
+  for (int e = 0; e < FGM_NEQ; ++e) if (!x.solver.count(fgm_eq_name(e))) x.solver[fgm_eq_name(e)] = SolverCfg{20, 1e-5, 0.0};
+}
 bool tci_name(const std::string& n) {
   for (const char* s : {"tci_kappa", "tci_tmix", "tci_tauStar", "tci_tc", "RR_eff", "Qdot_eff"}) if (n == s) return true;
   return false;
@@ -440,6 +485,44 @@ void ras_correct(Ctx& x) {
   ras_solve(x, 1);
   ras_nut(x);
 }
+// flareFGM::correct() (include/dfmi.h, flareFGM block): the transport equations in baseFGM::transport()'s order, each
+// assembled from the fields as they stand, solved, boundary-corrected, exchanged and clipped; Ha; the retrieval.
+void fgm_solve(Ctx& x, int eq) {
+  const char* nm = fgm_eq_name(eq);
+  Matrix& A = x.mK;
+  fgm_assemble(x, eq);
+  solve_bicgstab(x, nm, 1, nullptr, A.lower, 0, A.upper, 0, A.diag, 0, A.source, 0, A.ic, A.bc, 0, nm, x.f(nm), 0, x.solver[nm]);
+  fgm_post_solve(x, eq);
+}
+// what flareFGM needs of the context, refused by name
+void fgm_check(Ctx& x, const char* who) {
+  const std::string w = std::string(who) + ": ";
+  DFMI_CHECK(x.fgm.have_table, w + "no flamelet table set (dfmi_fgm_set_table)");
+  DFMI_CHECK(x.ras.model == 1, w + "flareFGM needs ras.model = 1 (the retrieval divides by k)");
+  DFMI_CHECK(!x.les.model, w + "flareFGM with les.model != 0 is not available (magUPrime needs an LESfilter)");
+  DFMI_CHECK(!x.tci.model, w + "flareFGM and tci.model != 0 exclude each other (one combustion model at a time)");
+  DFMI_CHECK(x.chem.mode == 0, w + "flareFGM with chemistry mode != 0 is not available (the table replaces the chemistry)");
+  DFMI_CHECK(!x.thermo.eos, w + "flareFGM with an equation of state set (dfmi_thermo_set_eos model 1) is not available");
+  ensure_fgm_fields(x);
+  for (int e = 0; e < FGM_NEQ; ++e)
+    DFMI_CHECK(x.stype.count(fgm_eq_name(e)), w + "patch types not set for field '" + fgm_eq_name(e) + "' (dfmi_set_patch_types)");
+  static const char* names[4] = {"k", "epsilon", "boundary_k", "boundary_epsilon"};
+  for (int i = 0; i < 4; ++i) DFMI_CHECK(x.ras.have[i], w + "the field '" + names[i] + "' is not set (dfmi_set_field)");
+}
+// several ranks: the neighbour half of the six scalars' processor slots as the caller set them (the gradients and the
+// limiter read the cell across a processor face; later calls find what fgm_post_solve left)
+void fgm_halo(Ctx& x) { halo_fields(x, {"Z", "Zvar", "c", "cvar", "Zcvar", "Ha"}); }
+void fgm_correct(Ctx& x) {
+  fgm_check(x, "dfmi_fgm_correct");
+  fgm_halo(x);
+  if (!x.ras.valid) ras_nut(x);   // mut = rho nut of k and epsilon as they stand
+  fgm_solve(x, 0);
+  fgm_solve(x, 1);
+  if (x.on("fgm.combustion")) { fgm_solve(x, 2); fgm_solve(x, 3); fgm_solve(x, 4); }
+  if (x.on("fgm.solveEnthalpy")) fgm_solve(x, 5);
+  else fgm_ha_from_z(x);
+  fgm_retrieve(x, true);
+}
 // step.hbya_early applies: the two-stream step on one rank (several ranks keep today's order: HbyA's field halo
 // stays behind the Y and E solves' exchanges)
 bool hbya_early(const Ctx& x) {
@@ -621,7 +704,8 @@ int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* patch_type
     std::string f(field);
     static const char* ok[] = {"U", "p", "he", "K", "Y", "T", "rho", "nut", "k", "epsilon"};
     const bool ras = f == "k" || f == "epsilon";
-    DFMI_CHECK(std::find_if(std::begin(ok), std::end(ok), [&](const char* s) { return f == s; }) != std::end(ok),
+    const bool fgm = fgm_eq_index(f) >= 0;   // the flareFGM scalars
+    DFMI_CHECK(fgm || std::find_if(std::begin(ok), std::end(ok), [&](const char* s) { return f == s; }) != std::end(ok),
                "unknown patch-type field '" + f + "'");
     for (int p = 0; p < x.P; ++p) {
       const int t = patch_type[p];
@@ -636,6 +720,8 @@ int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* patch_type
         DFMI_CHECK(x.pt("calculated")[p] != EMPTY, "patch " + std::to_string(p) + ": " + wn + " on an empty patch");
         continue;
       }
+      DFMI_CHECK(!fgm || t == ZERO_GRADIENT || t == FIXED_VALUE || t == EMPTY || t == CYCLIC || bc_proc(t),
+                 "patch " + std::to_string(p) + ": " + f + " takes zeroGradient, fixedValue, cyclic, processor, processorCyclic or empty");
       DFMI_CHECK(t != WAVE_TRANSMISSIVE || f == "p", "waveTransmissive is supported for p (the 1D flame's outlet)");
       DFMI_CHECK(t != INLET_OUTLET || f == "U" || f == "p" || f == "Y" || f == "K" || ras,
                  "inletOutlet is supported for U, p, Y, K, k and epsilon (energy needs its own mixed form)");
@@ -649,6 +735,7 @@ int dfmi_set_patch_types(dfmi_ctx* ctx, const char* field, const int* patch_type
                  "patch " + std::to_string(p) + ": nut takes zeroGradient, fixedValue, calculated, cyclic, processor, processorCyclic or empty");
     }
     if (ras) ensure_ras_fields(x);
+    if (fgm) ensure_fgm_fields(x);
     if (ras || f == "nut") {
       // nut belongs to these patch types too: a wall function's slots are formed by correctNut(). The tables are needed
       // from the first of the four codes on and are dropped with the last
@@ -763,7 +850,12 @@ int dfmi_set_scheme(dfmi_ctx* ctx, const char* term, const char* scheme) {
     } else if (t == "div(phi,k)" || t == "div(phi,epsilon)") {
       DFMI_CHECK(kind == SCH_UPWIND || kind == SCH_LINEAR || kind == SCH_LL, t + ": upwind, limitedLinear or linear");
       if (t == "div(phi,k)") { x.sch.tk = kind; x.sch.k_tk = k; } else { x.sch.teps = kind; x.sch.k_teps = k; }
-    } else throw Error("dfmi: unknown scheme term '" + t + "' (div(phi,Yi_h), div(phi,K), div(hDiffCorrFlux), div(phi,U), div(phi,k), div(phi,epsilon), laplacian)");
+    } else if (t.size() > 9 && t.rfind("div(phi,", 0) == 0 && t.back() == ')' && fgm_eq_index(t.substr(8, t.size() - 9)) >= 0) {
+      const int e = fgm_eq_index(t.substr(8, t.size() - 9));   // the flareFGM scalars (fvSchemes:35-43 of the fgm cases)
+      DFMI_CHECK(kind == SCH_UPWIND || kind == SCH_LL || kind == SCH_LL01, t + ": upwind, limitedLinear or limitedLinear01");
+      x.sch.fgm[e] = kind; x.sch.k_fgm[e] = k;
+    } else throw Error("dfmi: unknown scheme term '" + t + "' (div(phi,Yi_h), div(phi,K), div(hDiffCorrFlux), div(phi,U), div(phi,k), div(phi,epsilon), "
+                       "div(phi,Z), div(phi,Zvar), div(phi,c), div(phi,cvar), div(phi,Zcvar), div(phi,Ha), laplacian)");
   });
 }
 
@@ -893,6 +985,10 @@ int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long cou
     if (n == "delta" || n == "nut" || n == "boundary_nut") ensure_les_fields(x);
     if (ras_name(n)) ensure_ras_fields(x);
     if (n == "rho_thermo" || n == "boundary_rho_thermo") ensure_eos_fields(x);
+    if (fgm_name(n)) {
+      DFMI_CHECK(n != "fgm_Su" && n != "fgm_D" && n != "boundary_fgm_D", "field '" + n + "' is formed by the flareFGM transport and cannot be set");
+      ensure_fgm_fields(x);
+    }
     if (tci_name(n)) {
       DFMI_CHECK(n == "tci_tc", "field '" + n + "' is formed by dfmi_combustion_correct and cannot be set");
       ensure_tci_fields(x);
@@ -925,6 +1021,7 @@ int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, in
     if (n == "delta" || n == "nut" || n == "boundary_nut") ensure_les_fields(ctx->x);
     if (ras_name(n)) ensure_ras_fields(ctx->x);
     if (n == "rho_thermo" || n == "boundary_rho_thermo") ensure_eos_fields(ctx->x);
+    if (fgm_name(n)) ensure_fgm_fields(ctx->x);
     if (n == "boundary_yPlus") ensure_wall_fields(ctx->x);
     if (tci_name(n)) ensure_tci_fields(ctx->x);
     copy_field(ctx->x, n, host, count, layout, false);
@@ -938,13 +1035,51 @@ int dfmi_U_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); le
 int dfmi_Y_process(dfmi_ctx* ctx) {
   return guard([&] {
     require_ready(ctx->x);
+    DFMI_CHECK(!ctx->x.fgm.model, "dfmi_Y_process is not available with fgm.model = 1 (flareFGM solves no species equations: dfmi_fgm_correct)");
     ctx->x.dnn.prepared = false;   // a compaction left by an interrupted time step belongs to an old T
     les_effective(ctx->x);
     do_Y(ctx->x);
     if (ctx->x.chem.mode == 1) chem_check(ctx->x);   // the Y solve's polls have passed the chemistry
   });
 }
-int dfmi_E_process(dfmi_ctx* ctx) { return guard([&] { require_ready(ctx->x); les_effective(ctx->x); do_E(ctx->x); }); }
+int dfmi_E_process(dfmi_ctx* ctx) {
+  return guard([&] {
+    require_ready(ctx->x);
+    DFMI_CHECK(!ctx->x.fgm.model, "dfmi_E_process is not available with fgm.model = 1 (flareFGM solves no energy equation: dfmi_fgm_correct)");
+    les_effective(ctx->x);
+    do_E(ctx->x);
+  });
+}
+// flareFGM (include/dfmi.h, flareFGM block)
+int dfmi_fgm_set_table(dfmi_ctx* ctx, const int* dims, const double* axes, double Hfu, double Hox, const double* laminar,
+                       const double* tables, const double* d2Yeq, const double* d1Yeq, const int* species_index,
+                       const int* omega_index) {
+  return guard([&] {
+    DFMI_CHECK(ctx, "null context");
+    Ctx& x = ctx->x;
+    fgm_set_table(x, dims, axes, Hfu, Hox, laminar, tables, d2Yeq, d1Yeq, species_index, omega_index);
+    if (x.have_bgeom) ensure_fgm_fields(x);
+  });
+}
+int dfmi_fgm_retrieve(dfmi_ctx* ctx) {
+  return guard([&] {
+    DFMI_CHECK(ctx, "null context");
+    Ctx& x = ctx->x;
+    require_ready(x);
+    fgm_check(x, "dfmi_fgm_retrieve");
+    fgm_retrieve(x, false);
+    DFMI_HIP(hipStreamSynchronize(x.stream));
+  });
+}
+int dfmi_fgm_correct(dfmi_ctx* ctx) {
+  return guard([&] {
+    DFMI_CHECK(ctx, "null context");
+    Ctx& x = ctx->x;
+    require_ready(x);
+    fgm_correct(x);
+    DFMI_HIP(hipStreamSynchronize(x.stream));
+  });
+}
 // turbulence->correct() (dfLowMachFoam.C:508)
 int dfmi_turbulence_correct(dfmi_ctx* ctx) {
   return guard([&] {
@@ -975,6 +1110,8 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
       bool done = false;
       ~TimerReset() { if (!done) t.used = 0; }
     } treset{x.steptimer};
+    const bool fgm = x.fgm.model != 0;
+    if (fgm) fgm_check(x, "dfmi_time_step with fgm.model = 1");
     const bool eos = x.thermo.eos != 0;
     if (eos) {   // the real-fluid step is the laminar, non-reacting one (include/dfmi.h dfmi_thermo_set_eos)
       const char* why = "dfmi_time_step: with an equation of state set (dfmi_thermo_set_eos model 1) ";
@@ -992,16 +1129,25 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
     if (x.chem.mode == 2) dnn_prepare(x);   // reacting cells of this step's T (read after the UEqn polls)
     rho_process(x, false);          // rhoEqn (first PIMPLE iteration)
     les_effective(x);               // LES: muEff, alphaEff, mut / Sct from this rho (laminar: nothing)
-    const bool early = n_corr > 0 && hbya_early(x);   // the first corrector's HbyA right after the U solve
+    const bool early = !fgm && n_corr > 0 && hbya_early(x);   // the first corrector's HbyA right after the U solve
+    if (fgm) {
+      // flareFGM (dfLowMachFoam.C:328-455): no YEqn, no EEqn, no correctThermo; combustion->correct() writes T, psi, mu,
+      // the table species, rho and rho_thermo
+      do_U(x);
+      fgm_correct(x);
+    } else {
     do_U_Y_E(x, early);             // UEqn, YEqn, EEqn (one rank: the chemistry and YEqn assembly beside the
                                     // UEqn, the EEqn assembly beside the Y solve)
     thermo_correct(x, false);       // correctThermo
+    }
     // Equation of state: thermo.rho_ (rho_thermo) is no longer psi p, so the corrector is the CPU solver's (pEqn.H:1-4, 8,
     // 95): rho = thermo.rho(), psip0 = psi p, the p equation, thermo.rho_ += psi p - psip0. Its closing rhoEqn writes a
     // rho that the next statement -- rho = thermo.rho() of the next corrector, or after the loop (dfLowMachFoam.C:517) --
     // overwrites before anything in this laminar step reads it, as in the ideal-gas loop below.
-    for (int i = 0; eos && i < n_corr; ++i) {
-      if (i > 0) thermo_rho_from_psi(x);   // rho = rho_thermo (the first corrector's: correctThermo wrote both)
+    // flareFGM runs the same corrector (the retrieval wrote rho and rho_thermo) and keeps the closing rhoEqn of the last
+    // one, whose rho kEpsilon::correct() reads (the RAS tail of the ideal-gas loop).
+    for (int i = 0; (eos || fgm) && i < n_corr; ++i) {
+      if (i > 0) thermo_rho_from_psi(x);   // rho = rho_thermo (the first corrector's: correctThermo / the retrieval wrote both)
       thermo_psip0(x);
       if (i > 0 || !early) u_hbya(x);
       const int keep = (int)x.opt("amg.reuse_steps");
@@ -1010,8 +1156,9 @@ int dfmi_time_step(dfmi_ctx* ctx, int n_corr) {
       do_p(x);
       x.amg.reuse_ok = false;
       thermo_correct_psip_rho(x);          // rho_thermo += psi p - psip0
+      if (fgm && i == n_corr - 1) rho_process(x, false);
     }
-    for (int i = 0; !eos && i < n_corr; ++i) {   // pEqn_GPU.H
+    for (int i = 0; !eos && !fgm && i < n_corr; ++i) {   // pEqn_GPU.H
       // rho = psi p: the first corrector's is what correctThermo just wrote (the same product of the same p and psi,
       // halo included); psip0 = psi p feeds only correctPsipRho, skipped below (the field is not updated here)
       if (i > 0) thermo_rho_from_psi(x);
@@ -1255,6 +1402,12 @@ int dfmi_assemble(dfmi_ctx* ctx, const char* eqn) {
       ras_wall_update(x);
       ras_assemble(x, e == "k" ? 1 : 0);
     }
+    else if (fgm_eq_index(e) >= 0) {   // a flareFGM transport equation from the fields as they stand, no solve in between
+      fgm_check(x, "dfmi_assemble");
+      fgm_halo(x);
+      if (!x.ras.valid) ras_nut(x);
+      fgm_assemble(x, fgm_eq_index(e));
+    }
     else if (e == "p") {
       p_assemble(x);
       // corrected laplacian: the source of the corrector loop's first pass (do_p_nonorth)
@@ -1274,7 +1427,7 @@ int dfmi_get_matrix(dfmi_ctx* ctx, const char* eqn, const char* part, double* ho
     Ctx& x = ctx->x;
     std::string e(eqn), p(part);
     Matrix* A = e == "U" ? &x.mU : e == "Y" ? &x.mY : e == "E" ? &x.mE : e == "p" ? &x.mP
-                : (e == "k" || e == "epsilon") ? &x.mK : nullptr;   // k / epsilon: the scalar assembly's, whichever it formed last
+                : (e == "k" || e == "epsilon" || fgm_eq_index(e) >= 0) ? &x.mK : nullptr;   // the scalar assembly's, whichever it formed last
     DFMI_CHECK(A, "unknown equation '" + e + "'");
     DevBuf<double>* b = p == "lower" ? &A->lower : p == "upper" ? &A->upper : p == "diag" ? &A->diag :
                         p == "source" ? &A->source : p == "source_solve" ? &A->source_solve :
@@ -1308,7 +1461,7 @@ int dfmi_get_solver_rows(dfmi_ctx* ctx, const char* eqn, const char* part, doubl
 int dfmi_set_solver(dfmi_ctx* ctx, const char* eqn, int max_iter, double tol, double abs_tol) {
   return guard([&] {
     std::string e(eqn);
-    DFMI_CHECK(e == "U" || e == "Y" || e == "E" || e == "p" || e == "k" || e == "epsilon", "unknown equation '" + e + "'");
+    DFMI_CHECK(e == "U" || e == "Y" || e == "E" || e == "p" || e == "k" || e == "epsilon" || fgm_eq_index(e) >= 0, "unknown equation '" + e + "'");
     DFMI_CHECK(max_iter > 0 && tol >= 0 && abs_tol >= 0, "bad solver controls");
     SolverCfg& c = ctx->x.solver[e];
     c.max_iter = max_iter; c.tol = tol; c.abs_tol = abs_tol;
@@ -1452,6 +1605,7 @@ int dfmi_zero_d_step(dfmi_ctx* ctx, double dt, int n_steps) {
     Ctx& x = ctx->x;
     require_ready(x);
     DFMI_CHECK(dt > 0 && n_steps >= 1, "0D step: dt and n_steps must be positive");
+    DFMI_CHECK(!x.fgm.model, "dfmi_zero_d_step is not available with fgm.model = 1 (the reactor's chemistry is the mechanism's, not the table's)");
     DFMI_CHECK(!x.thermo.eos, "dfmi_zero_d_step is not available with an equation of state set (dfmi_thermo_set_eos model 1): "
                               "the reactor's chemistry is the ideal-gas one");
     x.dnn.prepared = false;
@@ -1554,6 +1708,8 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
       DFMI_CHECK(k != "les.model" || value == 0.0 || !x.tci.model,
                  "dfmi_set_option: les.model != 0 and tci.model != 0 exclude each other");
       if (value != x.opt(key)) { x.les.valid = false; x.les.zeroed = false; }
+      DFMI_CHECK(k != "les.model" || value == 0.0 || !x.fgm.model,
+                 "dfmi_set_option: les.model != 0 and fgm.model = 1 exclude each other (magUPrime needs an LESfilter)");
       if (k == "les.model") x.les.model = (int)value;
       if (x.les.model && x.have_bgeom) ensure_les_fields(x);
     }
@@ -1568,8 +1724,29 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
         DFMI_CHECK(value > 0 && value <= 1.79769313486231570e308, "dfmi_set_option: " + k + " must be positive and finite");
       // nut belongs to the model and its coefficients: one rule, as for les.*
       if (value != x.opt(key)) { x.ras.valid = false; x.les.valid = false; x.les.zeroed = false; }
+      DFMI_CHECK(k != "ras.model" || value == 1.0 || !x.fgm.model,
+                 "dfmi_set_option: ras.model = 0 is refused while fgm.model = 1 (the retrieval divides by k)");
       if (k == "ras.model") x.ras.model = (int)value;
       if (x.ras.model && x.have_bgeom) ensure_ras_fields(x);
+    }
+    if (k.rfind("fgm.", 0) == 0) {
+      if (k == "fgm.model" || k == "fgm.combustion" || k == "fgm.solveEnthalpy" || k == "fgm.flameletT")
+        DFMI_CHECK(value == 0.0 || value == 1.0, "dfmi_set_option: " + k + " must be 0 or 1");
+      else if (k == "fgm.incompPref")
+        DFMI_CHECK(value >= -1.79769313486231570e308 && value <= 1.79769313486231570e308, "dfmi_set_option: fgm.incompPref must be finite");
+      else
+        DFMI_CHECK(value > 0 && value <= 1.79769313486231570e308, "dfmi_set_option: " + k + " must be positive and finite");
+      if (k == "fgm.model" && value == 1.0) {
+        const char* why = "dfmi_set_option: fgm.model = 1 ";
+        DFMI_CHECK(x.fgm.have_table, std::string(why) + "needs a flamelet table (dfmi_fgm_set_table first)");
+        DFMI_CHECK(x.ras.model == 1, std::string(why) + "needs ras.model = 1 (the retrieval divides by k)");
+        DFMI_CHECK(!x.les.model, std::string(why) + "and les.model != 0 exclude each other (magUPrime needs an LESfilter)");
+        DFMI_CHECK(!x.tci.model, std::string(why) + "and tci.model != 0 exclude each other (one combustion model at a time)");
+        DFMI_CHECK(x.chem.mode == 0, std::string(why) + "is not available with chemistry mode != 0 (the table replaces the chemistry)");
+        DFMI_CHECK(!x.thermo.eos, std::string(why) + "is not available with an equation of state set (dfmi_thermo_set_eos model 1)");
+        if (x.have_bgeom) ensure_fgm_fields(x);
+      }
+      if (k == "fgm.model") x.fgm.model = (int)value;
     }
     if (k.rfind("tci.", 0) == 0) {
       const auto one_of = [&](std::initializer_list<double> vs) { bool ok = false; for (double v : vs) ok |= value == v; return ok; };
@@ -1594,6 +1771,8 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
       else
         DFMI_CHECK(value > 0 && value <= 1.79769313486231570e308, "dfmi_set_option: " + k + " must be positive and finite");
       if ((k == "tci.model" || k == "tci.chemistry") && value != x.opt(key)) tci_reset_tc(x);
+      DFMI_CHECK(k != "tci.model" || value == 0.0 || !x.fgm.model,
+                 "dfmi_set_option: tci.model != 0 and fgm.model = 1 exclude each other (one combustion model at a time)");
       if (k == "tci.model") x.tci.model = (int)value;
     }
     x.opts[k] = value;
@@ -1616,7 +1795,7 @@ int dfmi_get_option(dfmi_ctx* ctx, const char* key, double* value) {
 int dfmi_set_preconditioner(dfmi_ctx* ctx, const char* eqn, const char* name) {
   return guard([&] {
     std::string e(eqn), n(name);
-    DFMI_CHECK(e == "U" || e == "Y" || e == "E" || e == "p" || e == "k" || e == "epsilon", "unknown equation '" + e + "'");
+    DFMI_CHECK(e == "U" || e == "Y" || e == "E" || e == "p" || e == "k" || e == "epsilon" || fgm_eq_index(e) >= 0, "unknown equation '" + e + "'");
     DFMI_CHECK(n == "jacobi" || (n == "amg" && e == "p"), "preconditioner must be 'jacobi' or ('amg' for p)");
     ctx->x.solver[e].precond = n == "amg" ? 1 : 0;
   });

@@ -60,7 +60,20 @@ struct Schemes {
   double k_yh = 1.0, k_K = 1.0, k_U = 1.0;
   int tk = SCH_UPWIND, teps = SCH_UPWIND;   // div(phi,k), div(phi,epsilon) (RAS)
   double k_tk = 1.0, k_teps = 1.0;
+  // div(phi,Z), div(phi,Zvar), div(phi,c), div(phi,cvar), div(phi,Zcvar), div(phi,Ha) (flareFGM; fgm_eq_names order)
+  int fgm[6] = {SCH_UPWIND, SCH_UPWIND, SCH_UPWIND, SCH_UPWIND, SCH_UPWIND, SCH_UPWIND};
+  double k_fgm[6] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
 };
+// the flareFGM transport equations in the order they are solved (baseFGM::transport(), baseFGM.C:736-904)
+constexpr int FGM_NEQ = 6;
+inline const char* fgm_eq_name(int e) {
+  static const char* n[FGM_NEQ] = {"Z", "Zvar", "c", "cvar", "Zcvar", "Ha"};
+  return n[e];
+}
+inline int fgm_eq_index(const std::string& s) {
+  for (int e = 0; e < FGM_NEQ; ++e) if (s == fgm_eq_name(e)) return e;
+  return -1;
+}
 
 struct Field {
   DevBuf<double> buf;
@@ -104,6 +117,24 @@ struct Thermo {
   int eos = 0;
   std::vector<double> eos_a, eos_b, eos_w;
   DevBuf<double> dsqa, dkap, drsTc, deb;
+};
+
+// flareFGM flamelet table (dfmi_fgm_set_table; fgm.hip). On the device the NS + NY value tables are stored
+// corner-major, tab[loc (NS + NY) + variable]: the variables of one table corner are one contiguous run, so a lane's 64
+// corner gathers each touch one or two lines whatever the number of variables it reads there. d2Yeq / d1Yeq interleaved.
+struct Fgm {
+  int model = 0;                 // option fgm.model
+  bool have_table = false, scaled = true;
+  int n[6] = {0, 0, 0, 0, 0, 0}; // NH NZ NC NGZ NGC NZC
+  int NS = 0, NYomega = 0, NY = 0, NZL = 0;
+  long N = 0;                    // entries of one value table
+  double Hfu = 0, Hox = 0;
+  DevBuf<double> axes;           // the six axes, one after the other
+  DevBuf<double> lam;            // [5][NH NZL]: z, sl, th, tau, kctau
+  DevBuf<double> tab;            // [N][NS + NY]
+  DevBuf<double> dyeq;           // [NH NZ NGZ][2]: d2Yeq, d1Yeq (scaled PV only)
+  DevBuf<int> ysp;               // mechanism index of each table species [NY]
+  std::vector<int> h_ysp, h_osp; // and of the NYomega source species (host: names of omega_Yi's components)
 };
 
 struct Halo;   // RCCL processor-patch exchange (halo.hip)
@@ -311,6 +342,15 @@ inline const OptDef* option_defs(int& n) {
     {"tci.exp1", 0},                  // EDC exponents: 0 the version's own, otherwise 1..4
     {"tci.exp2", 0},
     {"tci.bad_tauStar", 0},           // get only: cells of the last EDC correct whose tauStar was not positive and finite
+    {"fgm.model", 0},                 // combustion->correct(): 0 none, 1 flareFGM (include/dfmi.h)
+    {"fgm.combustion", 0},            // flareFGMCoeffs combustion: the c, cvar and Zcvar equations and the source lookups
+    {"fgm.solveEnthalpy", 0},         // the Ha equation (off: Ha = Z (Hfu - Hox) + Hox)
+    {"fgm.flameletT", 0},             // T from the table (off: (Ha - Hf) / Cp + 298.15)
+    {"fgm.Sct", 0.7},                 // D = mut / Sct + mu / Sc
+    {"fgm.Sc", 1.0},
+    {"fgm.incompPref", -10.0},        // > 0: rho = incompPref psi; otherwise rho = p psi
+    {"fgm.TMin", 200.0},              // T clipped to [TMin, TMax]
+    {"fgm.TMax", 5000.0},
     {"p.n_nonorth", 0},               // nNonOrthogonalCorrectors (system/fvSolution PIMPLE): extra passes of the pEqn's
                                       // non-orthogonal corrector loop (pEqn.H:51-62)
   };
@@ -461,6 +501,7 @@ struct Ctx {
   std::map<std::string, int> solve_expect;   // iterations of the last solve per equation (linsolve.hip Poller)
   DevBuf<double> work;           // per equation (U, Y, E, p): system-iterations, summed on the device
   DevBuf<double> work_ras;       // the same for epsilon and k (allocated by their first solve)
+  DevBuf<double> work_fgm;       // the same for the six flareFGM equations (allocated by their first solve)
   KernelTimer ktimer;
   StepTimer steptimer;
   CommStats comm;
@@ -492,6 +533,7 @@ struct Ctx {
   // dropped YEqn / EEqn terms, the LES instantiations of the assemblies)
   // combustion closure (options tci.*, chem.hip tci_*): the model in force; bad: the device count of EDC cells without a usable tauStar
   struct Tci { int model = 0; DevBuf<int> bad; } tci;
+  Fgm fgm;                       // flareFGM: the table and the model in force (options fgm.*)
   // the chemistry source the YEqn assemblies read: the closure's kappa RR, or the chemistry's own RR
   double* rr_src() { return f(tci.model ? "RR_eff" : "RR"); }
   bool turbulent() const { return les.model != 0 || ras.model != 0; }
@@ -624,6 +666,18 @@ void ras_nut(Ctx& x);
 // set) and the per-slot / per-patch tables after a change. ras_inlet_k: boundary_k_ref from boundary_U. ras_wall_update:
 // epsilon, G and boundary_epsilon of the wall cells, the constraint flags, boundary_epsilon_ref. ras_correct and
 // dfmi_assemble call ras_inlet_k, ras_production, ras_wall_update in that order.
+// flareFGM (include/dfmi.h, flareFGM block). fgm_set_table (fgm.hip): the checks and the upload. fgm_retrieve
+// (fgm.hip): flareFGM::retrieval() on cells and slots, then the halo; write_rho = false leaves cell rho alone (the
+// constructor's call, timeIndex 0). fgm_assemble (fv_kernels.hip): one transport equation's diffusivity, source and matrix
+// into Ctx::mK from the fields as they stand. fgm_post_solve: boundary values, halo, the clip to the field's bounds.
+// fgm_ha_from_z: Ha = Z (Hfu - Hox) + Hox on cells and slots. The solves between them are the caller's (capi.cpp fgm_correct).
+void fgm_set_table(Ctx& x, const int* dims, const double* axes, double Hfu, double Hox, const double* laminar,
+                   const double* tables, const double* d2Yeq, const double* d1Yeq, const int* species_index,
+                   const int* omega_index);
+void fgm_retrieve(Ctx& x, bool write_rho);
+void fgm_assemble(Ctx& x, int eq);
+void fgm_post_solve(Ctx& x, int eq);
+void fgm_ha_from_z(Ctx& x);
 void ras_wall_refresh(Ctx& x, bool inlets);
 void ras_inlet_k(Ctx& x);
 void ras_wall_update(Ctx& x);

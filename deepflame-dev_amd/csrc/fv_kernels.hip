@@ -3452,6 +3452,128 @@ void ras_wall_update(Ctx& x) {
            x.f("boundary_epsilon_ref"));
   }
 }
+
+// ---- flareFGM transport (include/dfmi.h, flareFGM block): baseFGM::transport(), the non-spray branch
+namespace {
+// D = (rho nut) / Sct + mu / Sc over n cells or n boundary slots (each slot from its own boundary values)
+__global__ void k_fgm_diffusivity(long n, double Sct, double Sc, const double* __restrict__ rho, const double* __restrict__ nut,
+                                  const double* __restrict__ mu, double* __restrict__ D) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  D[i] = (rho[i] * nut[i]) / Sct + mu[i] / Sc;
+}
+// the explicit source per unit volume of equation eq (0 Z, 1 Zvar, 2 c, 3 cvar, 4 Zcvar, 5 Ha), with a = ((2 mut) / Sct) (g1 . g2),
+// g1 . g2 = (x x + y y) + z z of the Gauss gradients g1, g2 [3][n], mut = rho nut:
+//   Zvar:  a(gZ, gZ) - (2 rho) chi_Z         cvar:   (a(gc, gc) - (2 rho) chi_c) + 2 (cOmega_c - omega_c c)
+//   c:     omega_c                           Zcvar:  (a(gZ, gc) - (2 rho) chi_Zc) + (ZOmega_c - omega_c Z)          Z, Ha: 0
+struct FgmSrc {
+  const double *rho, *nut, *g1, *g2, *chi, *omc, *xOmc, *psi;
+};
+__global__ void k_fgm_source(long n, int eq, double Sct, FgmSrc s, double* __restrict__ Su) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (eq == 0 || eq == 5) { Su[i] = 0.0; return; }
+  if (eq == 2) { Su[i] = s.omc[i]; return; }
+  const double r = s.rho[i];
+  const double dot = (s.g1[i] * s.g2[i] + s.g1[n + i] * s.g2[n + i]) + s.g1[2 * n + i] * s.g2[2 * n + i];
+  const double a = ((2.0 * (r * s.nut[i])) / Sct) * dot;
+  const double v = a - (2.0 * r) * s.chi[i];
+  if (eq == 1) Su[i] = v;
+  else if (eq == 3) Su[i] = v + 2.0 * (s.xOmc[i] - s.omc[i] * s.psi[i]);
+  else Su[i] = v + (s.xOmc[i] - s.omc[i] * s.psi[i]);
+}
+// psi.min(hi); psi.max(lo) over n cells or slots
+__global__ void k_fgm_clip(long n, double lo, double hi, double* __restrict__ psi) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double v = psi[i];
+  v = v < hi ? v : hi;
+  v = v > lo ? v : lo;
+  psi[i] = v;
+}
+__global__ void k_fgm_ha(long n, double Hfu, double Hox, const double* __restrict__ Z, double* __restrict__ Ha) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Ha[i] = Z[i] * (Hfu - Hox) + Hox;
+}
+}  // namespace
+
+// the Gauss gradient of the flareFGM field nm into the buffer `buf` ([3][C]; its processor slots through the halo)
+static double* fgm_grad(Ctx& x, const char* nm, const char* buf) {
+  const MeshView m = x.view();
+  const std::string bn = std::string("boundary_") + nm, bb = std::string("boundary_") + buf;
+  double* g = scheme_buf(x, buf, x.C, 3);
+  scheme_buf(x, bb.c_str(), x.B, 3);
+  LAUNCH_GRAD(1, x.st(nm), x.f(nm), x.f(bn), g);
+  halo_fields(x, {buf});
+  return g;
+}
+void fgm_assemble(Ctx& x, int eq) {
+  const char* nm = fgm_eq_name(eq);
+  const std::string bn = std::string("boundary_") + nm;
+  const MeshView m = x.view();
+  Matrix& A = x.mK;
+  const double Sct = x.opt("fgm.Sct"), Sc = x.opt("fgm.Sc");
+  const int8_t* ty = x.st(nm);
+  LAUNCH(k_fgm_diffusivity, x.C, (long)x.C, Sct, Sc, x.f("rho"), x.f("nut"), x.f("mu"), x.f("fgm_D"));
+  LAUNCH(k_fgm_diffusivity, x.B, (long)x.B, Sct, Sc, x.f("boundary_rho"), x.f("boundary_nut"), x.f("boundary_mu"),
+         x.f("boundary_fgm_D"));
+  // the gradients of Z and c as they stand (inside correct(): just solved and clipped)
+  FgmSrc s{x.f("rho"), x.f("nut"), nullptr, nullptr, nullptr, x.f("omega_c"), nullptr, nullptr};
+  if (eq == 1) { s.g1 = s.g2 = fgm_grad(x, "Z", "fgm_gradZ"); s.chi = x.f("chi_Z"); }
+  else if (eq == 3) { s.g1 = s.g2 = fgm_grad(x, "c", "fgm_gradc"); s.chi = x.f("chi_c"); s.xOmc = x.f("cOmega_c"); s.psi = x.f("c"); }
+  else if (eq == 4) {
+    s.g1 = fgm_grad(x, "Z", "fgm_gradZ"); s.g2 = fgm_grad(x, "c", "fgm_gradc");
+    s.chi = x.f("chi_Zc"); s.xOmc = x.f("ZOmega_c"); s.psi = x.f("Z");
+  }
+  LAUNCH(k_fgm_source, x.C, (long)x.C, eq, Sct, s, x.f("fgm_Su"));
+  const int kind = x.sch.fgm[eq];
+  const bool lim = kind == SCH_LL || kind == SCH_LL01, corr = x.lap == LAP_CORRECTED;
+  double *g = nullptr, *bg = nullptr;
+  if (lim || corr) {   // the field's own Gauss gradient: the limiter's upwind-cell gradient and the corrected laplacian's
+    if (lim) scheme_checks(x, true);
+    g = fgm_grad(x, nm, "fgm_grad");
+    bg = x.f("boundary_fgm_grad");
+  }
+  const double *w = nullptr, *bw = nullptr;
+  if (lim) {
+    double* wo = scheme_buf(x, "fgm_w", x.Fs, 1, true);
+    double* bwo = scheme_buf(x, "boundary_fgm_w", x.B, 1);
+    const double twoByk = 2.0 / std::max(x.sch.k_fgm[eq], 1e-15);
+    const int b01 = kind == SCH_LL01 ? 1 : 0;
+    if (face_hex(x)) LAUNCH(k_lim_w_cell, x.C, m, b01, twoByk, x.f("phi"), x.f(nm), g, wo);
+    else LAUNCH(k_lim_w_face, x.Fs, m, b01, twoByk, x.f("phi"), x.f(nm), g, wo);
+    LAUNCH(k_lim_w_slot, x.B, m, ty, b01, twoByk, x.f("boundary_phi"), x.f(nm), x.f(bn), g, bg, bwo);
+    w = wo; bw = bwo;
+  }
+  LAUNCH_W(k_scalar_assemble, x.C, m, ty, x.f(nm), x.f(bn), x.f("rho"), x.f("rho_old"), x.f("phi"), x.f("boundary_phi"),
+           x.f("fgm_D"), x.f("boundary_fgm_D"), x.f("fgm_Su"), x.f("fgm_Sp"), A.lower.p, A.upper.p, A.diag.p, A.source.p,
+           A.ic.p, A.bc.p, mixbc(x, nm), w, bw);
+  if (corr) {   // - fvm::laplacian(D, psi): the explicit non-orthogonal term
+    NoArgs a = no_args(x);
+    a.g = g; a.bg = bg;
+    a.gam = x.f("fgm_D"); a.bgam = x.f("boundary_fgm_D");
+    a.src = A.source.p;
+    LAUNCH_NO(1, NO_SHARED, ty, a);
+  }
+}
+// after the solve: the field's boundary values and halo (fvMatrix::solve's correctBoundaryConditions), then
+// psi.min(upper); psi.max(lower) on cells and slots (pointwise: the processor slots' neighbour halves stay the
+// neighbour cells' values)
+void fgm_post_solve(Ctx& x, int eq) {
+  const char* nm = fgm_eq_name(eq);
+  const std::string bn = std::string("boundary_") + nm;
+  k_bc_correct(x, nm, x.f(nm), x.f(bn), 1);
+  halo_fields(x, {nm});
+  static const double lo[FGM_NEQ] = {0.0, 0.0, 0.0, 0.0, -0.25, 0.0}, hi[FGM_NEQ] = {1.0, 0.25, 1.0, 0.25, 0.25, 0.0};
+  if (eq == 5) return;   // Ha is not clipped
+  LAUNCH(k_fgm_clip, x.C, (long)x.C, lo[eq], hi[eq], x.f(nm));
+  LAUNCH(k_fgm_clip, x.B, (long)x.B, lo[eq], hi[eq], x.f(bn));
+}
+void fgm_ha_from_z(Ctx& x) {
+  LAUNCH(k_fgm_ha, x.C, (long)x.C, x.fgm.Hfu, x.fgm.Hox, x.f("Z"), x.f("Ha"));
+  LAUNCH(k_fgm_ha, x.B, (long)x.B, x.fgm.Hfu, x.fgm.Hox, x.f("boundary_Z"), x.f("boundary_Ha"));
+}
 #undef LAUNCH_GRAD
 #undef LAUNCH_NO
 
@@ -3522,7 +3644,7 @@ double hbm_copy_gbs(Ctx& x, size_t bytes, int reps) {
 }
 
 void thermo_rho_from_psi(Ctx& x) {   // dfThermo::updateRho (dfThermo.cu:673-679)
-  if (x.thermo.eos) {   // rho = thermo.rho(), which with an equation of state is rho_thermo and not psi p
+  if (x.thermo.eos || x.fgm.model) {   // rho = thermo.rho(): with an equation of state, or flareFGM, rho_thermo and not psi p
     DFMI_HIP(hipMemcpyAsync(x.f("rho"), x.f("rho_thermo"), sizeof(double) * x.C, hipMemcpyDeviceToDevice, x.stream));
     if (x.B > 0)
       DFMI_HIP(hipMemcpyAsync(x.f("boundary_rho"), x.f("boundary_rho_thermo"), sizeof(double) * x.B, hipMemcpyDeviceToDevice,
@@ -3537,7 +3659,7 @@ void thermo_psip0(Ctx& x) {          // dfThermo::psip0 (:681-686)
   LAUNCH(k_mul, x.B, (long)x.B, x.f("boundary_psi"), x.f("boundary_p"), x.f("boundary_psip0"));
 }
 void thermo_correct_psip_rho(Ctx& x) {   // dfThermo::correctPsipRho (:688-695)
-  if (x.thermo.eos) {   // thermo.rho_ += psi p - psip0
+  if (x.thermo.eos || x.fgm.model) {   // thermo.rho_ += psi p - psip0
     LAUNCH(k_add_psip, x.C, (long)x.C, x.f("p"), x.f("psi"), x.f("psip0"), x.f("rho_thermo"));
     LAUNCH(k_add_psip, x.B, (long)x.B, x.f("boundary_p"), x.f("boundary_psi"), x.f("boundary_psip0"), x.f("boundary_rho_thermo"));
     return;

@@ -1406,6 +1406,7 @@ int work_slot(const std::string& eqn) {
   if (eqn == "p") return 3;
   if (eqn == "epsilon") return 4;   // 4, 5: Ctx::work_ras
   if (eqn == "k") return 5;
+  if (fgm_eq_index(eqn) >= 0) return 6 + fgm_eq_index(eqn);   // 6 .. 11: Ctx::work_fgm
   throw Error("dfmi: unknown equation '" + eqn + "'");
 }
 
@@ -1431,9 +1432,10 @@ void record_stats(Ctx& x, const char* eqn, const double* scal, int nsys, const d
   sn.h.ensure_mapped((size_t)nsys * NSCAL);
   sn.nsys = nsys;
   const int slot = work_slot(eqn);
-  if (slot >= 4 && x.work_ras.n == 0) { x.work_ras.alloc(2); x.work_ras.zero(x.stream); }
-  hipLaunchKernelGGL(k_accum_iters, dim3(1), dim3(64), 0, x.stream, scal, nsys, slot < 4 ? x.work.p + slot : x.work_ras.p + (slot - 4),
-                     sn.h.d, flag);
+  if (slot >= 4 && slot < 6 && x.work_ras.n == 0) { x.work_ras.alloc(2); x.work_ras.zero(x.stream); }
+  if (slot >= 6 && x.work_fgm.n == 0) { x.work_fgm.alloc(FGM_NEQ); x.work_fgm.zero(x.stream); }
+  hipLaunchKernelGGL(k_accum_iters, dim3(1), dim3(64), 0, x.stream, scal, nsys,
+                     slot < 4 ? x.work.p + slot : slot < 6 ? x.work_ras.p + (slot - 4) : x.work_fgm.p + (slot - 6), sn.h.d, flag);
 }
 
 }  // namespace
@@ -1803,8 +1805,8 @@ void bicg_rows_get(Ctx& x, int nsys, const std::string& part, double* host, long
 
 double solver_work(Ctx& x, const std::string& eqn, bool reset) {
   const int k = work_slot(eqn);
-  if ((k < 4 ? x.work.n : x.work_ras.n) == 0) return 0.0;
-  double* at = k < 4 ? x.work.p + k : x.work_ras.p + (k - 4);
+  if ((k < 4 ? x.work.n : k < 6 ? x.work_ras.n : x.work_fgm.n) == 0) return 0.0;
+  double* at = k < 4 ? x.work.p + k : k < 6 ? x.work_ras.p + (k - 4) : x.work_fgm.p + (k - 6);
   double v = 0.0;
   DFMI_HIP(hipMemcpyAsync(&v, at, sizeof(double), hipMemcpyDeviceToHost, x.stream));
   DFMI_HIP(hipStreamSynchronize(x.stream));

@@ -86,6 +86,8 @@ SIGNATURES = {
     "dfmi_chem_set_options": [_P, C.c_int, C.c_double, C.c_double, C.c_double],
     "dfmi_chem_solve": [_P, C.c_double],
     "dfmi_combustion_correct": [_P, C.c_double],
+    "dfmi_fgm_set_table": [_P, _IP, _DP, C.c_double, C.c_double, _DP, _DP, _DP, _DP, _IP, _IP],
+    "dfmi_fgm_retrieve": [_P], "dfmi_fgm_correct": [_P],
     "dfmi_chem_set_max_steps": [_P, C.c_int],
     "dfmi_zero_d_step": [_P, C.c_double, C.c_int],
     "dfmi_renumber_cells": [C.c_int, _DP, C.c_int, _IP, _IP, C.c_char_p, _IP],
@@ -360,6 +362,30 @@ class Context:
         """combustion->correct() (include/dfmi.h dfmi_combustion_correct; options tci.*): the chemistry solve and, with
         a PaSR or EDC closure in force, kappa and the scaled source RR_eff / Qdot_eff. tci.model = 0: chem_solve(dt)."""
         self._call("dfmi_combustion_correct", self.h, float(dt))
+
+    def fgm_set_table(self, table, species_index, omega_index):
+        """the flamelet table of flareFGM (include/dfmi.h dfmi_fgm_set_table); table: a dfmi.fgm.Table"""
+        dims = _i32(table.dims())
+        axes = _f64(np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in table.axes]))
+        lam = _f64(table.laminar)
+        tabs = _f64(table.values)
+        d2 = _f64(table.d2Yeq) if table.scaled else None
+        d1 = _f64(table.d1Yeq) if table.scaled else None
+        ysp, osp = _i32(species_index), _i32(omega_index)
+        if ysp.size == 0:
+            ysp = np.zeros(1, np.int32)
+        if osp.size == 0:
+            osp = np.zeros(1, np.int32)
+        self._call("dfmi_fgm_set_table", self.h, _ip(dims), _dp(axes), float(table.Hfu), float(table.Hox), _dp(lam), _dp(tabs),
+                   _dp(d2) if d2 is not None else None, _dp(d1) if d1 is not None else None, _ip(ysp), _ip(osp))
+
+    def fgm_retrieve(self):
+        """flareFGM::retrieval() as the constructor calls it: cell rho is left alone (include/dfmi.h dfmi_fgm_retrieve)"""
+        self._call("dfmi_fgm_retrieve", self.h)
+
+    def fgm_correct(self):
+        """flareFGM::correct(): transport, Ha, retrieval (include/dfmi.h dfmi_fgm_correct)"""
+        self._call("dfmi_fgm_correct", self.h)
 
     def zero_d_step(self, dt, n_steps=1):
         """df0DFoam time steps on every cell (include/dfmi.h dfmi_zero_d_step)"""

@@ -68,6 +68,13 @@ def scheme_codes(schemes: dict) -> tuple[list, list]:
     return codes, ks
 
 
+def strip_comments(txt: str) -> str:
+    """OpenFOAM dictionary text without its /* */ and // comments"""
+    import re
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return re.sub(r"//.*", "", txt)
+
+
 def dict_entries(txt: str) -> list:
     """the `keyword value...;` entries of a piece of OpenFOAM dictionary text in file order, as
     (keyword, value) pairs; // and /* */ comments are dropped, and so is every { } block with its name

@@ -150,7 +150,8 @@ int dfmi_set_traversal(dfmi_ctx* ctx, const int* order);
 /* ---- per-equation patch types ------------------------------------------------------------ */
 /* dfUEqn/dfYEqn/dfEEqn/dfpEqn/dfRhoEqn/dfThermo::setConstantFields (e.g. dfUEqn.cu:364-379,
  * dfEEqn.cu setConstantFields, dfThermo.cu setConstantFields). field in
- * {"U","p","he","K","Y","T","rho","nut","k","epsilon"}; patch_type[num_patches]. "nut" (LES / RAS, below) takes zeroGradient, fixedValue,
+ * {"U","p","he","K","Y","T","rho","nut","k","epsilon"} and the flareFGM scalars {"Z","Zvar","c","cvar","Zcvar","Ha"} (flareFGM
+ * block below); patch_type[num_patches]. "nut" (LES / RAS, below) takes zeroGradient, fixedValue,
  * calculated, cyclic, processor, processorCyclic and empty; not set, it is "calculated" on every non-coupled patch
  * (OpenFOAM's default for nut: the stored boundary_nut is kept, zero unless set).
  * The k-epsilon wall functions and turbulent inlets (RAS block below) have codes of their own, each for one field, on plain
@@ -201,7 +202,8 @@ int dfmi_thermo_set_eos(dfmi_ctx* ctx, int model, int num_species, const double*
  *        RAS: k epsilon (cells), boundary_{k,epsilon}, boundary_{k,epsilon}_ref; get only: G divU k_prebound epsilon_prebound,
  *        boundary_yPlus (the nutkWallFunction slots' yPlus, zero elsewhere).
  *        Combustion closure: tci_tc (cells); get only: tci_kappa tci_tmix tci_tauStar Qdot_eff (cells), RR_eff (species).
- *        Equation of state: rho_thermo, boundary_rho_thermo (thermo.rho_; allocated at the first dfmi_thermo_set_eos or use). */
+ *        Equation of state: rho_thermo, boundary_rho_thermo (thermo.rho_; allocated at the first dfmi_thermo_set_eos or use).
+ *        flareFGM: the fields of the flareFGM block below. */
 int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long count, int layout);
 int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, int layout);
 
@@ -370,7 +372,7 @@ int dfmi_hbm_copy_peak(dfmi_ctx* ctx, double gib, int reps, double* gbs);
 int dfmi_correct_boundary(dfmi_ctx* ctx, const char* field);
 
 /* ---- matrix inspection (the reference DEBUG_CHECK_LDU / compareResult path, dfYEqn.cu:566-572) */
-/* eqn in {"rho","U","Y","E","p","HbyA","Y_ell","Y_ell_ref","epsilon","k","tci"}: run that equation's assembly only (no solve); under
+/* eqn in {"rho","U","Y","E","p","HbyA","Y_ell","Y_ell_ref","epsilon","k","tci","Z","Zvar","c","cvar","Zcvar","Ha"}: run that equation's assembly only (no solve); under
  * the laplacian scheme "corrected" the sources include the explicit term ("p": that of the corrector loop's first pass).
  * "tci" (tci.model != 0): the closure's pointwise passes of dfmi_combustion_correct from the fields as they stand, RR and Qdot
  * included, without the chemistry solve -- tci_tmix, tci_tc, tci_kappa (PaSR) or tci_kappa, tci_tauStar (EDC), then RR_eff
@@ -384,7 +386,8 @@ int dfmi_get_matrix(dfmi_ctx* ctx, const char* eqn, const char* part, double* ho
  * part "val" [S-1][W][C] (W = coupling entries per row), "dS" (diag + internalCoeffs) or "rhs"
  * [S-1][C]. eqn must be "Y". */
 int dfmi_get_solver_rows(dfmi_ctx* ctx, const char* eqn, const char* part, double* host, long count);
-/* solver controls (amgxUOptions / amgxpOptions): eqn in {"U","Y","E","p","epsilon","k"} */
+/* solver controls (amgxUOptions / amgxpOptions): eqn in {"U","Y","E","p","epsilon","k"} and the flareFGM equations
+ * {"Z","Zvar","c","cvar","Zcvar","Ha"} */
 int dfmi_set_solver(dfmi_ctx* ctx, const char* eqn, int max_iter, double tol, double abs_tol);
 /* preconditioner: "jacobi" (all) or "amg" (p; aggregation AMG V-cycle, the amgxpOptions
  * AGGREGATION solver's role) -- p defaults to "amg", U/Y/E to "jacobi" */
@@ -401,6 +404,7 @@ int dfmi_set_preconditioner(dfmi_ctx* ctx, const char* eqn, const char* name);
  * "ras.*" (model, Cmu, C1, C2, C3, sigmak, sigmaEps, kMin, epsilonMin, Prt, Sct: the same call's RAS block),
  * "tci.*" (model, mixing, chemistry, Cmix, fuel, oxidizer, CO2, H2, version, C1, C2, Cgamma, Ctau, exp1, exp2:
  * dfmi_combustion_correct below),
+ * "fgm.*" (model, combustion, solveEnthalpy, flameletT, Sct, Sc, incompPref, TMin, TMax: the flareFGM block below),
  * "dnn.tuned_gemm", "step.courant" (1: dfmi_time_step queues the Courant-number kernel behind its last
  * kernel and posts the result to pinned memory for dfmi_courant_no; 0, the default: nothing added); keys and
  * defaults in INTEGRATION.md. Solver-structure keys must be set before the first solve; unknown keys fail. */
@@ -510,6 +514,85 @@ int dfmi_chem_solve(dfmi_ctx* ctx, double dt);
  * call the chemistry. Returns non-zero when a cell hit the step limit, as the solve does. The CPU-A baseline keeps the keys
  * and refuses tci.model != 0 by name. */
 int dfmi_combustion_correct(dfmi_ctx* ctx, double dt);
+/* ---- flareFGM: combustion->correct() with combustionModel flareFGM (dfLowMachFoam.C:328-455; src/dfCombustionModels/FGM/
+ * baseFGM/baseFGM.C:478-912, flareFGM/flareFGM.C:122-762, flameletTableSolver/tableSolver.C; the reference computes it on the
+ * host). The non-LES, non-spray branch; DESIGN.md 18. The statement below is the definition.
+ * Options (dfmi_set_option; an unknown fgm.* key is refused by name):
+ *   fgm.model 0 none (default) | 1 flareFGM;   fgm.combustion, fgm.solveEnthalpy, fgm.flameletT  0 (default) | 1
+ *   fgm.Sct 0.7, fgm.Sc 1, fgm.TMin 200, fgm.TMax 5000 (positive and finite);   fgm.incompPref -10 (any finite value)
+ * Table (dfmi_fgm_set_table): dims[10] = NH NZ NC NGZ NGC NZC NS NYomega NY NZL; axes = the six axes h, z, c, gz, gc, gzc
+ * one after the other; laminar [5][NH NZL] = z, sl, th, tau, kctau; tables [NS + NY][NH NZ NC NGZ NGC NZC] in the reference's
+ * index order (readThermChemTables.H: variable v of grid point (h, z, c, gz, gc, gzc), the last index fastest) -- variables
+ * 0..7 = omgc, cOc, ZOc, cp, mwt, hiyi, Tf, nu, then the NYomega source terms, then (unscaled only) Ycmax, then the NY species;
+ * d2Yeq, d1Yeq [NH NZ NGZ] when NS == 8 + NYomega (scaled progress variable), not read (may be null) when NS == 9 + NYomega
+ * (unscaled); species_index [NY] and omega_index [NYomega]: the mechanism indices of the table's species and of its source
+ * species. Call it after dfmi_set_constant_values. Refused by name: any other NS; a dimension < 1; NZL < 2; an axis (or a row
+ * of the laminar z) that is not strictly increasing; a value that is not finite; a species index outside [0, num_species);
+ * value tables of more than 2^28 entries in all (2 GiB; the host transposes them once).
+ * These checks keep every gather index inside its table; the kernels clamp through locate / intfac only.
+ * Lookups (tableSolver.C:425-498, 602-869): locate(n, a, x) = 0 for n == 1 or x <= a[0], n - 2 for x >= a[n-1], else the i with
+ * a[i] <= x < a[i+1]; fac = 0 for x <= low, 1 for x >= high, 0 for high - low < 1e-30, else (x - low) / (high - low); AN AXIS
+ * OF LENGTH 1 HAS fac = 0 (the reference reads a[1] past the end there: DESIGN.md 9). With w(i, f) = (1 - f) + i (2 f - 1),
+ * i = 0, 1, a 6-D lookup is  sum over i0..i5 (i0 outermost) of  (((((w0 w1) w2) w3) w4) w5) table[corner],  accumulated as
+ * result = result + factor * value; the upper corner index of an axis is loc + 1 where its length > 1, else loc. lookup2d on
+ * the laminar block locates z on the block's FIRST row (tableSolver.C:782-795 passes z_Tb5 itself); lookup3d is (h, z, gz).
+ * Fields (cells and boundary_<name>; allocated at the first use of the model): Z Zvar c cvar Zcvar Ha (set / get; patch types
+ * of the same names: zeroGradient, fixedValue, cyclic, processor, processorCyclic, empty); get: chi_Z chi_Zc chi_c omega_c
+ * cOmega_c ZOmega_c Ha_s c_s Zvar_s cvar_s Zcvar_s Wt Cp Hf (Wt, Cp, Hf start at 28.96, 1010.1, 1907), omega_Yi [NYomega]
+ * (component j: the source term of species omega_index[j]), fgm_D, fgm_Su; the retrieval also writes T, psi, mu, rho,
+ * rho_thermo and the NY table species of Y.
+ * dfmi_fgm_retrieve: flareFGM::retrieval() as the constructor calls it, per cell and per boundary slot from the slot's own
+ * values, in this order (small = 1e-4, smaller = 1e-6, SMALL = 1e-15; max / min are (a > b ? a : b) / (a < b ? a : b)):
+ *   chi_Z = eps / k Zvar;  chi_Zc = eps / k Zcvar;  hLoss = min(max((Z (Hfu - Hox) + Hox) - Ha, h[0]), h[NH-1]);  ih = locate(h, hLoss)
+ *   Zl = z_lam[ih][0], Zr = z_lam[ih][NZL-1];  flame = Z >= Zl && Z <= Zr && fgm.combustion && c > small
+ *   flame:  kc_s, tau, sl, dl = lookup2d(hLoss, Z) of kctau, tau, sl, th;  nu = mu / rho (both as they stand on entry)
+ *           Ka = (dl / (sl + SMALL)) / (sqrt(nu / eps) + SMALL);  Kc = kc_s tau;  C3 = 1.5 sqrt(Ka) / (1 + sqrt(Ka));
+ *           C4 = 1.1 / pow(1 + Ka, 0.4);  chi_c = rho / 6.7 cvar ((2 Kc - tau C4) sl / (dl + SMALL) + C3 eps / (k + SMALL))
+ *   else:   chi_c = eps / k cvar  (cells),  eps / (k + SMALL) cvar  (slots)
+ *   gvar(m, v, Y) = max(smaller, min(1, m < small || m > 1 - small ? 0 : v / (m ((Y < 0 ? 1 : Y) - m))))
+ *   gz = gvar(Z, Zvar, -1);  gcz = fmax(-1, fmin(1, cvar < 1e-4 || Zvar < 1e-6 ? 0 : Zcvar / (sqrt(Zvar) sqrt(cvar))))
+ *   scaled: Ycmax = -1, cNorm = c;  unscaled: Ycmax = max(smaller, lookup6d(hLoss, Z, 0, gz, 0, 0) of table NS - 1), cNorm = c / Ycmax
+ *   gc = gvar(c, cvar, Ycmax);  every other lookup6d is at (hLoss, Z, cNorm, gz, gc, gcz)
+ *   flame:  omega_c = table 0 + (scaled ? chi_Z c lookup3d(d2Yeq) + 2 chi_Zc lookup3d(d1Yeq) : 0);  cOmega_c = table 1;
+ *           ZOmega_c = table 2;   else all three 0;   then each times rho (as it stands on entry)
+ *   Ha_s = hLoss, c_s = cNorm, Zvar_s = gz, cvar_s = gc, Zcvar_s = gcz;  Wt = table 4;  mu = table 7 times rho (on entry)
+ *   Y[species_index[j]] = table NS + j;  omega_Yi[j] = table NS - NYomega + j
+ *   fgm.flameletT: T = table 6 (Cp, Hf untouched);  else Cp = table 3, Hf = table 5, T = (Ha - Hf) / Cp + 298.15
+ *   T = min(max(T, TMin), TMax);  psi = Wt / (8.314e3 T)
+ *   slots: rho = rho_thermo = (incompPref > 0 ? incompPref : p) psi.  cells: rho is left alone (timeIndex == 0,
+ *   flareFGM.C:747) and rho_thermo = rho.
+ * Empty slots are untouched, processor [internal n] slots copy their cell, and the results cross processor patches in one
+ * exchange afterwards (several ranks: a collective), as dfmi_thermo_correct's do. Kernels k_fgm_retrieve_cells /
+ * k_fgm_retrieve_slots.
+ * dfmi_fgm_correct: flareFGM::correct(). First transport(), each equation
+ *   ddt(rho, psi) + div(phi, psi) - laplacian(D, psi) == Su,   D = (rho nut) / Sct + mu / Sc  (cells and slots alike)
+ * through the k and epsilon equations' generic assembly (dfmi_turbulence_correct, RAS block: Euler ddt with rho_old and the
+ * field's own value, the laplacian scheme in force) with Sp = 0, solved under its own name ("Z", "Zvar", "c", "cvar", "Zcvar",
+ * "Ha": dfmi_set_solver / _stats / _work, dfmi_assemble / dfmi_get_matrix), its boundary values corrected and exchanged, then
+ * clipped on cells and slots, psi = max(min(psi, upper), lower):  Z [0, 1], Zvar [0, 0.25], c [0, 1] (cMax_ stays 1 in both PV
+ * modes: baseFGM.C:805 assigns Ycmaxall_, which is never set from the table), cvar [0, 0.25], Zcvar [-0.25, 0.25]; Ha is not
+ * clipped. Order Z, Zvar, then with fgm.combustion c, cvar, Zcvar, then with fgm.solveEnthalpy Ha. Su per unit volume, with
+ * mut = rho nut, a(g1, g2) = ((2 mut) / Sct) ((g1x g2x + g1y g2y) + g1z g2z) and the Gauss gradients of Z and c as they stand
+ * (just solved and clipped), chi_* and the omegas as the previous retrieval left them:
+ *   Z: 0    Zvar: a(gZ, gZ) - (2 rho) chi_Z    c: omega_c    cvar: (a(gc, gc) - (2 rho) chi_c) + 2 (cOmega_c - omega_c c)
+ *   Zcvar: (a(gZ, gc) - (2 rho) chi_Zc) + (ZOmega_c - omega_c Z)    Ha: 0
+ * div(phi,Z) ... div(phi,Ha): dfmi_set_scheme, upwind (default) | limitedLinear <k> | limitedLinear01 <k>. Without
+ * fgm.solveEnthalpy, Ha = Z (Hfu - Hox) + Hox on every cell and slot. Last the retrieval above, which now also writes the
+ * cells' rho = rho_thermo = (incompPref > 0 ? incompPref : p) psi.
+ * dfmi_time_step with fgm.model = 1: rhoEqn; UEqn; dfmi_fgm_correct; per pressure corrector rho = rho_thermo, psip0 = psi p,
+ * the p equation, rho_thermo += psi p - psip0 (the corrector of dfmi_thermo_set_eos) and, in the last one, the rhoEqn;
+ * kEpsilon::correct(); rho = rho_thermo. No YEqn, no EEqn, no thermo call, no chemistry. While fgm.model = 1,
+ * dfmi_thermo_update_rho and dfmi_thermo_correct_psip_rho act on rho_thermo as under an equation of state.
+ * Refused by name: fgm.model = 1 without a table, with ras.model != 1, les.model != 0, tci.model != 0, chemistry mode != 0 or an
+ * equation of state set (at dfmi_set_option and again at the calls); dfmi_Y_process, dfmi_E_process and dfmi_zero_d_step while
+ * fgm.model = 1; k, epsilon or a patch-type set of the six scalars missing. With fgm.model = 0 every launch of every other
+ * entry is the one it was, and a context that never touches the model allocates what it did. The CPU-A baseline exports the
+ * three entries, keeps the keys and refuses fgm.model = 1 by name. */
+int dfmi_fgm_set_table(dfmi_ctx* ctx, const int* dims, const double* axes, double Hfu, double Hox, const double* laminar,
+                       const double* tables, const double* d2Yeq, const double* d1Yeq, const int* species_index,
+                       const int* omega_index);
+int dfmi_fgm_retrieve(dfmi_ctx* ctx);
+int dfmi_fgm_correct(dfmi_ctx* ctx);
 /* n_steps df0DFoam time steps (applications/solvers/df0DFoam/df0DFoam.C:99-113, YEqn.H, EEqn.H;
  * zeroDReactor constantProperty pressure): per step chemistry.solve(dt) on every cell, YEqn
  * ddt(rho, Yi) == RR_i (Yi.max(0), inert = 1 - sum), he held, correctThermo (T from he), rho = p psi.
