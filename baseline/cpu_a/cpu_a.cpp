@@ -111,6 +111,8 @@ struct Ctx {
   std::map<std::string, double> fgm = {{"fgm.model", 0}, {"fgm.combustion", 0}, {"fgm.solveEnthalpy", 0}, {"fgm.flameletT", 0},
                                        {"fgm.Sct", 0.7}, {"fgm.Sc", 1.0}, {"fgm.incompPref", -10.0}, {"fgm.TMin", 200.0},
                                        {"fgm.TMax", 5000.0}};
+  // spray coupling (options spray.*): the keys and defaults of the HIP library, accepted and kept; spray.model = 1 is refused by name
+  std::map<std::string, double> spray = {{"spray.model", 0}, {"spray.rho", 0}, {"spray.U", 0}, {"spray.Yi", 0}, {"spray.h", 0}};
   struct Les { int model = 0; double Ck = 0.094, Ce = 1.048, Cw = 0.325, Prt = 1.0, Sct = 1.0; bool valid = false, have_delta = false; } les;
   bool step_courant = false;   // option step.courant: accepted for the callers that set it; the number is always computed on demand
   bool have_sizes = false, have_topo = false, have_geom = false, have_bgeom = false;
@@ -176,6 +178,9 @@ void allocate_fields(Ctx& x) {
   alloc(x, "chem_stats", C, 3);
   alloc(x, "delta", C, 1); alloc(x, "nut", C, 1); alloc(x, "boundary_nut", B, 1);   // LES
   alloc(x, "Qdot", C, 1);   // heat release -sum_i hc_i RR_i (dfChemistryModel.C:771)
+  // spray coupling: the field names of the HIP library, kept; the terms themselves are its alone (spray.model = 1 is refused)
+  alloc(x, "parcel_rhoTrans", C, S); alloc(x, "parcel_UTrans", C, 3);
+  alloc(x, "parcel_UCoeff", C, 1); alloc(x, "parcel_hsTrans", C, 1); alloc(x, "parcel_hsCoeffByCp", C, 1);
   const long ns = std::max(S, 3);
   auto wk = [&](const std::string& n, long len) { x.work[n].assign(std::max(len, 1L), 0.0); };
   wk("out_lower", (long)S * F); wk("out_upper", (long)S * F); wk("out_diag", (long)S * C);
@@ -1347,6 +1352,17 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
       it->second = value;
       return;
     }
+    if (ctx && key && std::string(key).rfind("spray.", 0) == 0) {   // the keys of the HIP library; the terms themselves are its alone
+      const std::string k(key);
+      auto it = ctx->x.spray.find(k);
+      CHECK(it != ctx->x.spray.end(), "unknown option '" + k + "'");
+      if (k == "spray.model") {
+        CHECK(value == 0.0 || value == 1.0, "spray.model must be 0 (no cloud, or not coupled) or 1 (active and coupled)");
+        CHECK(value == 0.0, "spray.model = 1: CPU-A does not implement the parcel source terms (the HIP library)");
+      } else CHECK(value == 0.0 || value == 1.0, k + " must be 0 (explicit) or 1 (semiImplicit)");
+      it->second = value;
+      return;
+    }
     if (ctx && key && std::string(key).rfind("ras.", 0) == 0) {   // the keys of the HIP library; the model itself is its alone
       const std::string k(key);
       auto it = ctx->x.ras.find(k);
@@ -1383,6 +1399,12 @@ int dfmi_get_option(dfmi_ctx* ctx, const char* key, double* value) {
     if (ctx && key && value && std::string(key).rfind("fgm.", 0) == 0) {
       auto it = ctx->x.fgm.find(key);
       CHECK(it != ctx->x.fgm.end(), std::string("unknown option '") + key + "'");
+      *value = it->second;
+      return;
+    }
+    if (ctx && key && value && std::string(key).rfind("spray.", 0) == 0) {
+      auto it = ctx->x.spray.find(key);
+      CHECK(it != ctx->x.spray.end(), std::string("unknown option '") + key + "'");
       *value = it->second;
       return;
     }

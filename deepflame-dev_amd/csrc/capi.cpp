@@ -185,6 +185,20 @@ void ensure_fgm_fields(Ctx& x) {
   }
   for (int e = 0; e < FGM_NEQ; ++e) if (!x.solver.count(fgm_eq_name(e))) x.solver[fgm_eq_name(e)] = SolverCfg{20, 1e-5, 0.0};
 }
+// Spray coupling (options spray.*): the cloud's five transfer fields, cell fields without boundary
+// counterparts. Allocated (zeroed) when spray.model is first 1 or one of them is first touched: nothing in a context that
+// never mentions spray.
+int spray_index(const std::string& n) {
+  for (int i = 0; i < 5; ++i) if (n == spray_field_name(i)) return i;
+  return -1;
+}
+void ensure_spray_fields(Ctx& x) {
+  if (x.fields.count("parcel_rhoTrans")) return;
+  DFMI_CHECK(x.have_sizes, "call dfmi_set_constant_values first");
+  alloc_field(x, "parcel_rhoTrans", x.C, x.S, false);
+  alloc_field(x, "parcel_UTrans", x.C, 3, false);
+  for (auto n : {"parcel_UCoeff", "parcel_hsTrans", "parcel_hsCoeffByCp"}) alloc_field(x, n, x.C, 1, false);
+}
 bool tci_name(const std::string& n) {
   for (const char* s : {"tci_kappa", "tci_tmix", "tci_tauStar", "tci_tc", "RR_eff", "Qdot_eff"}) if (n == s) return true;
   return false;
@@ -999,6 +1013,16 @@ int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long cou
     DFMI_CHECK(n != "nut", "field 'nut' is formed by dfmi_turbulence_correct and cannot be set (boundary_nut holds the fixed-value slots)");
     DFMI_CHECK(n.rfind("nonorth_", 0) != 0 && n.rfind("boundary_nonorth_", 0) != 0,
                "field '" + n + "' is formed by the library (dfmi_set_scheme \"laplacian\") and cannot be set");
+    const int spi = spray_index(n);
+    if (spi >= 0) {   // the cloud's accumulators: every value finite, UCoeff (a sum of masses over time scales) not negative
+      ensure_spray_fields(x);
+      DFMI_CHECK(count == x.C, "field '" + n + "': expected " + std::to_string(x.C) + " values per component, got " + std::to_string(count));
+      const long tot = count * x.fields.at(n).ncomp;
+      for (long i = 0; i < tot; ++i) {
+        DFMI_CHECK(host[i] >= -1.79769313486231570e308 && host[i] <= 1.79769313486231570e308, "field '" + n + "': every value must be finite");
+        DFMI_CHECK(spi != 2 || host[i] >= 0, "field 'parcel_UCoeff': the coefficient must not be negative");
+      }
+    }
     if (n == "delta") {
       DFMI_CHECK(count == x.C, "field 'delta': expected " + std::to_string(x.C) + " values, got " + std::to_string(count));
       for (long i = 0; i < count; ++i)
@@ -1013,6 +1037,7 @@ int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long cou
     // RAS: nut belongs to k and epsilon and their boundary counterparts
     static const char* rk[4] = {"k", "epsilon", "boundary_k", "boundary_epsilon"};
     for (int i = 0; i < 4; ++i) if (n == rk[i]) { x.ras.have[i] = true; x.ras.valid = false; }
+    if (spi >= 0) x.spray.have[spi] = true;
   });
 }
 int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, int layout) {
@@ -1024,6 +1049,7 @@ int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, in
     if (fgm_name(n)) ensure_fgm_fields(ctx->x);
     if (n == "boundary_yPlus") ensure_wall_fields(ctx->x);
     if (tci_name(n)) ensure_tci_fields(ctx->x);
+    if (spray_index(n) >= 0) ensure_spray_fields(ctx->x);
     copy_field(ctx->x, n, host, count, layout, false);
   });
 }
@@ -1389,8 +1415,16 @@ int dfmi_assemble(dfmi_ctx* ctx, const char* eqn) {
       y_assemble_ell(x, x.ell.W, (long)x.C + x.H, val, dS, rhs);
     } else if (e == "Y_ell_ref") {    // LDU assembly folded by the generic solver gather
       YWs _yw(x);
-      y_prep(x); y_assemble(x);
+      // spray: the rows are folded from the LDU parts without the parcel terms, which then go into both forms as the
+      // last thing added -- the order y_assemble_ell keeps (dS = diag + internalCoeffs, then the term)
+      y_prep(x); y_assemble(x, false);
       bicg_rows_from_ldu_Y(x);
+      if (x.spray.model) {
+        spray_fold_y(x, x.mY.diag.p, x.mY.source.p, x.C, false);
+        double *val, *dS, *rhs;
+        bicg_layout(x, x.S - 1, &val, &dS, &rhs);
+        spray_fold_y(x, dS, rhs, (long)x.C + x.H, true);
+      }
     } else if (e == "E") { conv_weights(x); e_assemble(x); }   // EEqn inspected on its own: fresh div(phi,Yi_h) weights
     else if (e == "k" || e == "epsilon") {   // from the fields as they stand, no solve in between
       DFMI_CHECK(x.ras.model, "dfmi_assemble: '" + e + "' needs ras.model != 0");
@@ -1744,6 +1778,7 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
         DFMI_CHECK(!x.tci.model, std::string(why) + "and tci.model != 0 exclude each other (one combustion model at a time)");
         DFMI_CHECK(x.chem.mode == 0, std::string(why) + "is not available with chemistry mode != 0 (the table replaces the chemistry)");
         DFMI_CHECK(!x.thermo.eos, std::string(why) + "is not available with an equation of state set (dfmi_thermo_set_eos model 1)");
+        DFMI_CHECK(!x.spray.model, std::string(why) + "is not available with spray.model = 1 (the flareFGM spray branch is not on the device)");
         if (x.have_bgeom) ensure_fgm_fields(x);
       }
       if (k == "fgm.model") x.fgm.model = (int)value;
@@ -1774,6 +1809,19 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
       DFMI_CHECK(k != "tci.model" || value == 0.0 || !x.fgm.model,
                  "dfmi_set_option: tci.model != 0 and fgm.model = 1 exclude each other (one combustion model at a time)");
       if (k == "tci.model") x.tci.model = (int)value;
+    }
+    if (k.rfind("spray.", 0) == 0) {
+      if (k == "spray.model") {
+        DFMI_CHECK(value == 0.0 || value == 1.0, "dfmi_set_option: spray.model must be 0 (no cloud, or not coupled) or 1 (active and coupled)");
+        DFMI_CHECK(value == 0.0 || !x.fgm.model, "dfmi_set_option: spray.model = 1 is not available with fgm.model = 1 (the flareFGM spray branch is not on the device)");
+        DFMI_CHECK(value == 0.0 || !x.thermo.eos,
+                   "dfmi_set_option: spray.model = 1 is not available with an equation of state set (dfmi_thermo_set_eos model 1)");
+        if (value == 1.0 && x.have_sizes) ensure_spray_fields(x);
+        x.spray.model = (int)value;
+      } else {
+        DFMI_CHECK(value == 0.0 || value == 1.0, "dfmi_set_option: " + k + " must be 0 (explicit) or 1 (semiImplicit)");
+        x.spray.sch[k == "spray.rho" ? 0 : k == "spray.U" ? 1 : k == "spray.Yi" ? 2 : 3] = (int)value;
+      }
     }
     x.opts[k] = value;
   });

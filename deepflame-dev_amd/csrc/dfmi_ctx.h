@@ -351,6 +351,12 @@ inline const OptDef* option_defs(int& n) {
     {"fgm.incompPref", -10.0},        // > 0: rho = incompPref psi; otherwise rho = p psi
     {"fgm.TMin", 200.0},              // T clipped to [TMin, TMax]
     {"fgm.TMax", 5000.0},
+    {"spray.model", 0},               // the Lagrangian cloud's active && coupled: 1 adds the parcel source terms to the rho,
+                                      // U, Yi and he equations (include/dfmi.h, spray block)
+    {"spray.rho", 0},                 // sourceTerms.schemes of sprayCloudProperties: 0 explicit, 1 semiImplicit
+    {"spray.U", 0},
+    {"spray.Yi", 0},
+    {"spray.h", 0},
     {"p.n_nonorth", 0},               // nNonOrthogonalCorrectors (system/fvSolution PIMPLE): extra passes of the pEqn's
                                       // non-orthogonal corrector loop (pEqn.H:51-62)
   };
@@ -534,6 +540,9 @@ struct Ctx {
   // combustion closure (options tci.*, chem.hip tci_*): the model in force; bad: the device count of EDC cells without a usable tauStar
   struct Tci { int model = 0; DevBuf<int> bad; } tci;
   Fgm fgm;                       // flareFGM: the table and the model in force (options fgm.*)
+  // spray coupling (options spray.*, fv_kernels.hip spray_*): the model in force, the schemes of the rho, U, Yi and h
+  // terms (0 explicit, 1 semiImplicit), and which of the cloud's transfer fields the caller has set (spray_field_name order)
+  struct Spray { int model = 0; int sch[4] = {0, 0, 0, 0}; bool have[5] = {false, false, false, false, false}; } spray;
   // the chemistry source the YEqn assemblies read: the closure's kappa RR, or the chemistry's own RR
   double* rr_src() { return f(tci.model ? "RR_eff" : "RR"); }
   bool turbulent() const { return les.model != 0 || ras.model != 0; }
@@ -637,8 +646,19 @@ void u_hbya(Ctx& x);
 void p_assemble(Ctx& x, bool cell_pass = true);   // cell_pass = false: solve_pcg's fused setup writes diag and source
 void p_post_solve(Ctx& x);
 void y_prep(Ctx& x, bool weights = true);   // weights = false: the caller formed the div(phi,Yi_h) weights
-void y_assemble(Ctx& x);
+void y_assemble(Ctx& x, bool spray = true);   // spray = false: the caller adds the parcel terms itself (spray_fold_y)
 void y_assemble_ell(Ctx& x, int W, long Ce, double* val, double* dS, double* rhs);
+// Spray coupling (include/dfmi.h, spray block): the cloud's transfer fields folded into an equation's diag /
+// source as the last thing added to them. rho_process, u_assemble, y_assemble, y_assemble_ell and e_assemble_back call
+// these themselves; with spray.model = 0 they return at once and launch nothing. spray_on: the model is in force, after
+// the refusals (fgm.model, an equation of state, a required field never set). spray_fold_y: the species rows in LDU form
+// (ell = false: diag / source [S][C]) or in the solver's (ell = true: dS / rhs [S - 1][Ce], even-odd positions).
+inline const char* spray_field_name(int i) {
+  static const char* n[5] = {"parcel_rhoTrans", "parcel_UTrans", "parcel_UCoeff", "parcel_hsTrans", "parcel_hsCoeffByCp"};
+  return n[i];
+}
+bool spray_on(Ctx& x);
+void spray_fold_y(Ctx& x, double* diag, double* source, long stride, bool ell);
 void y_post_solve(Ctx& x);
 void e_assemble(Ctx& x);
 void e_assemble_front(Ctx& x);   // the scheme terms (independent of the Y solve)

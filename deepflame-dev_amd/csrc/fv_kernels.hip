@@ -658,6 +658,111 @@ __global__ void k_rho(MeshView m, const int8_t* __restrict__ ty, const double* _
   if (odiag) { odiag[c] = diag; osrc[c] = src; }
 }
 
+// ------------------------------------------------------------------ spray coupling (include/dfmi.h, spray block)
+// The cloud's per-cell transfer fields folded into the rho, U, Yi and he equations, each term the last thing added to
+// its diag / source, in the operation order include/dfmi.h states (-ffp-contract=off: no fused multiply-add). Streaming
+// per-cell passes: one thread per cell (per species for Yi), [S][C] reads coalesced, no atomics, no LDS. They run only
+// with spray.model = 1; every other kernel of this file is what it was.
+//
+// rhoEqn with parcels.Srho(rho) (rhoEqn.H:38): k_rho's cell with the term between the source and the diagonal solve.
+// semi: SuSp(s / rho, rho) with rho as it stands before this solve (ReactingCloudI.H:211-236).
+template <int WT>
+__global__ void k_rho_spray(MeshView m, const int8_t* __restrict__ ty, const double* __restrict__ rho_old,
+                            const double* __restrict__ phi, const double* __restrict__ bphi, double* __restrict__ rho,
+                            double* __restrict__ odiag, double* __restrict__ osrc, const double* __restrict__ rhoTrans,
+                            int S, int semi) {
+  const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
+  if (c >= m.C) return;
+  double div = 0.0;
+  each_face<WT>(m, c, [&](int f, int, bool own) { if (own) div += phi[f]; else div -= phi[f]; });
+  each_slot(m, ty, c, [&](int b, int) { div += bphi[b]; });
+  const double vol = m.V[c];
+  double diag = m.rdt * vol;
+  double src = m.rdt * rho_old[c] * vol;
+  src = src - div;
+  double sum = 0.0;
+  for (int i = 0; i < S; ++i) sum += rhoTrans[(long)i * m.C + c];
+  const double t = sum * m.rdt;
+  if (semi) {
+    const double r = rho[c];
+    const double a = (t / vol) / r;
+    diag = diag - vol * fmax(a, 0.0);
+    src = src + (vol * fmin(a, 0.0)) * r;
+  } else src = src + t;
+  rho[c] = src / diag;
+  if (odiag) { odiag[c] = diag; osrc[c] = src; }
+}
+// UEqn with parcels.SU(U) (UEqn.H:9). semi: UTrans - Sp(UCoeff, U) + UCoeff U (KinematicCloudI.H:432-437): the diagonal
+// takes UCoeff rdt, and rAU is formed again from it and the stored internalCoeffs as k_u_assemble forms it.
+__global__ void k_spray_u(MeshView m, const int8_t* __restrict__ tyU, int semi, const double* __restrict__ UTrans,
+                          const double* __restrict__ UCoeff, const double* __restrict__ U, double* __restrict__ diag,
+                          double* __restrict__ src, double* __restrict__ srcs, const double* __restrict__ ic,
+                          double* __restrict__ rAU) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= m.C) return;
+  const long C = m.C, B = m.B;
+  double uc = 0.0;
+  if (semi) {
+    uc = UCoeff[c];
+    const double dg = diag[c] + uc * m.rdt;
+    diag[c] = dg;
+    double r = dg;
+    each_slot(m, tyU, c, [&](int b, int) { r += (ic[b] + ic[B + b] + ic[2 * B + b]) / 3; });
+    rAU[c] = 1 / (r / m.V[c]);
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double t = semi ? (UTrans[k * C + c] + uc * U[k * C + c]) * m.rdt : UTrans[k * C + c] * m.rdt;
+    src[k * C + c] = src[k * C + c] + t;
+    srcs[k * C + c] = srcs[k * C + c] + t;
+  }
+}
+// YEqn with parcels.SYi(i, Yi) (YEqn.H:110-111), blockIdx.y = species; the inert species has no equation. ell: the
+// solver's rows (system index skips the inert species, row position eopos[c]) instead of the LDU arrays [S][C].
+// semi (ReactingCloudI.H:110-131): a sink goes to the diagonal over Yi + small, a source stays explicit.
+__global__ void k_spray_y(MeshView m, int inert, int semi, int ell, long stride, const double* __restrict__ rhoTrans,
+                          const double* __restrict__ Y, double* __restrict__ diag, double* __restrict__ src) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = blockIdx.y;
+  if (c >= m.C || i == inert) return;
+  const long C = m.C;
+  const long row = ell ? (long)(i < inert ? i : i - 1) * stride + (m.eopos ? m.eopos[c] : c) : (long)i * stride + c;
+  const double t = rhoTrans[i * C + c] * m.rdt;
+  if (semi) {
+    const double vol = m.V[c];
+    const double s = t / vol;
+    if (s < 0) diag[row] = diag[row] + (vol * (-s)) / (Y[i * C + c] + 1e-15);
+    else src[row] = src[row] + s * vol;
+  } else src[row] = src[row] + t;
+}
+// EEqn with parcels.Sh(he) and hcSource = sum_i rhoTrans_i hc_i / deltaT (EEqn.H:3-8, 27-28, 34-35). semi
+// (ThermoCloudI.H:236-245): hsTrans - SuSp(hsCoeff / Cp, he) + hsCoeff / Cp he, whose two he terms cancel where the
+// coefficient is negative.
+__global__ void k_spray_e(MeshView m, int S, int semi, const double* __restrict__ rhoTrans, const double* __restrict__ hc,
+                          const double* __restrict__ hsTrans, const double* __restrict__ hsCoeffByCp,
+                          const double* __restrict__ he, double* __restrict__ diag, double* __restrict__ src) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= m.C) return;
+  const long C = m.C;
+  const double sens = hsTrans[c] * m.rdt;
+  double s = src[c];
+  bool impl = false;
+  if (semi) {
+    const double vol = m.V[c];
+    const double a = (hsCoeffByCp[c] * m.rdt) / vol;
+    if (a >= 0) {
+      const double aV = a * vol;
+      diag[c] = diag[c] + aV;
+      s = s + (sens + aV * he[c]);
+      impl = true;
+    }
+  }
+  if (!impl) s = s + sens;
+  double h = 0.0;
+  for (int i = 0; i < S; ++i) h += rhoTrans[i * C + c] * hc[i];
+  src[c] = s + h * m.rdt;
+}
+
 // ------------------------------------------------------------------ Courant number
 // compressibleCourantNo.H of OpenFOAM-7 (dfLowMachFoam.C:261): sumPhi = fvc::surfaceSum(mag(phi)) / rho,
 // CoNum = 0.5 gMax(sumPhi / V) deltaT, meanCoNum = 0.5 (gSum(sumPhi) / gSum(V)) deltaT. One thread per cell sums
@@ -2755,9 +2860,50 @@ void copy_old(Ctx& x) {   // dfMatrixDataBase::preTimeStep (dfMatrixDataBase.cu:
 void rho_process(Ctx& x, bool write_matrix) {
   double* od = write_matrix ? x.f("dbg_rho_diag") : nullptr;
   double* os = write_matrix ? x.f("dbg_rho_source") : nullptr;
+  if (spray_on(x))
+    LAUNCH_W(k_rho_spray, x.C, x.view(), x.st("rho"), x.f("rho_old"), x.f("phi"), x.f("boundary_phi"), x.f("rho"), od, os,
+             x.f("parcel_rhoTrans"), x.S, x.spray.sch[0]);
+  else
   LAUNCH_W(k_rho, x.C, x.view(), x.st("rho"), x.f("rho_old"), x.f("phi"), x.f("boundary_phi"), x.f("rho"), od, os);
   k_bc_correct(x, "rho", x.f("rho"), x.f("boundary_rho"), 1);
   halo_fields(x, {"rho"});
+}
+
+// ---- spray coupling (include/dfmi.h, spray block)
+// spray.model = 0: false, nothing else. Otherwise the refusals by name, then true.
+bool spray_on(Ctx& x) {
+  if (!x.spray.model) return false;
+  const char* why = "spray.model = 1 ";
+  DFMI_CHECK(!x.fgm.model, std::string(why) + "is not available with fgm.model = 1 (the flareFGM spray branch is not on the device)");
+  DFMI_CHECK(!x.thermo.eos, std::string(why) + "is not available with an equation of state set (dfmi_thermo_set_eos model 1)");
+  DFMI_CHECK(x.thermo.dhc.n == (size_t)x.S, std::string(why) + "needs the thermo coefficients (dfmi_thermo_set_coeffs: hc_i)");
+  for (int i = 0; i < 5; ++i) {
+    const bool need = i == 2 ? x.spray.sch[1] == 1 : i == 4 ? x.spray.sch[3] == 1 : true;
+    DFMI_CHECK(!need || (x.spray.have[i] && x.fields.count(spray_field_name(i))),
+               std::string(why) + "needs the field '" + spray_field_name(i) + "', which was never set (dfmi_set_field)");
+  }
+  return true;
+}
+static void spray_fold_u(Ctx& x) {
+  if (!spray_on(x)) return;
+  Matrix& A = x.mU;
+  const int semi = x.spray.sch[1];
+  LAUNCH(k_spray_u, x.C, x.view(), x.st("U"), semi, x.f("parcel_UTrans"), semi ? x.f("parcel_UCoeff") : nullptr, x.f("U"),
+         A.diag.p, A.source.p, A.source_solve.p, A.ic.p, x.f("rAU"));
+}
+void spray_fold_y(Ctx& x, double* diag, double* source, long stride, bool ell) {
+  if (!spray_on(x)) return;
+  KScope _ks(x, "k_spray_y");
+  hipLaunchKernelGGL(k_spray_y, dim3(blocks_for(x.C, TPB), x.S), dim3(TPB), 0, x.stream, x.view(), x.inert, x.spray.sch[2],
+                     ell ? 1 : 0, stride, x.f("parcel_rhoTrans"), x.f("Y"), diag, source);
+  DFMI_HIP(hipGetLastError());
+}
+static void spray_fold_e(Ctx& x) {
+  if (!spray_on(x)) return;
+  Matrix& A = x.mE;
+  const int semi = x.spray.sch[3];
+  LAUNCH(k_spray_e, x.C, x.view(), x.S, semi, x.f("parcel_rhoTrans"), x.thermo.dhc.p, x.f("parcel_hsTrans"),
+         semi ? x.f("parcel_hsCoeffByCp") : nullptr, x.f("he"), A.diag.p, A.source.p);
 }
 
 // compressibleCourantNo.H: the per-cell gather, the fixed-order second stage and the record, queued on the context
@@ -2835,6 +2981,7 @@ void u_assemble(Ctx& x) {
            x.f("boundary_p"), x.f("tauU"), x.f("boundary_tauU"), A.lower.p, A.upper.p, A.diag.p, A.source.p,
            A.source_solve.p, A.ic.p, A.bc.p, x.f("rAU"), mixbc(x, "U"), x.sch_w(6), x.sch_w(7));
   if (x.lap == LAP_CORRECTED) nonorth_u(x);
+  spray_fold_u(x);   // parcels.SU(U): the last thing added (after the explicit non-orthogonal term); rAU under semiImplicit
   k_bc_correct(x, "extrapolated", x.f("rAU"), x.f("boundary_rAU"), 1);
   halo_fields(x, {"rAU"});
 }
@@ -3100,7 +3247,7 @@ void y_prep(Ctx& x, bool weights) {
   LAUNCH(k_phiuc_slot, x.B, m, x.st("Y"), x.f("sumYDiffError"), x.f("boundary_sumYDiffError"), x.f("boundary_phiUc"));
 }
 
-void y_assemble(Ctx& x) {
+void y_assemble(Ctx& x, bool spray) {
   Matrix& A = x.mY;
   MeshView m = x.view();
 #define CALL(NS) LAUNCH_SWL(k_y_assemble, NS, x.C, m, x.st("Y"), x.inert, x.f("Y"), x.f("boundary_Y"), x.f("rhoD"),   \
@@ -3112,6 +3259,7 @@ void y_assemble(Ctx& x) {
                        x.f("phiUc"), x.f("boundary_phiUc"), A.lower.p, A.upper.p, A.diag.p, A.source.p, A.ic.p, A.bc.p, mixbc(x, "Y"), x.sch_w(0), x.sch_w(1)))
 #undef CALL
   if (x.lap == LAP_CORRECTED) nonorth_y(x, A.source.p, nullptr, 0);
+  if (spray) spray_fold_y(x, A.diag.p, A.source.p, x.C, false);   // parcels.SYi(i, Yi), after the non-orthogonal term
 }
 
 void y_assemble_ell(Ctx& x, int W, long Ce, double* val, double* dS, double* rhs) {
@@ -3136,6 +3284,7 @@ void y_assemble_ell(Ctx& x, int W, long Ce, double* val, double* dS, double* rhs
 #undef GEN
 #undef CALL
   if (x.lap == LAP_CORRECTED) nonorth_y(x, nullptr, rhs, Ce);
+  spray_fold_y(x, dS, rhs, Ce, true);
 }
 
 void y_post_solve(Ctx& x) {
@@ -3162,6 +3311,7 @@ void e_assemble_back(Ctx& x) {
          eg, A.lower.p, A.upper.p, A.diag.p, A.source.p, A.ic.p, A.bc.p, x.sch_w(0), x.sch_w(1), x.sch_w(2),
          x.sch_w(3), x.sch_w(4), x.sch_w(5));
   if (x.lap == LAP_CORRECTED) nonorth_e(x);
+  spray_fold_e(x);   // parcels.Sh(he) and hcSource, after the non-orthogonal term
 }
 void e_assemble(Ctx& x) {
   e_assemble_front(x);

@@ -203,7 +203,9 @@ int dfmi_thermo_set_eos(dfmi_ctx* ctx, int model, int num_species, const double*
  *        boundary_yPlus (the nutkWallFunction slots' yPlus, zero elsewhere).
  *        Combustion closure: tci_tc (cells); get only: tci_kappa tci_tmix tci_tauStar Qdot_eff (cells), RR_eff (species).
  *        Equation of state: rho_thermo, boundary_rho_thermo (thermo.rho_; allocated at the first dfmi_thermo_set_eos or use).
- *        flareFGM: the fields of the flareFGM block below. */
+ *        flareFGM: the fields of the flareFGM block below.
+ *        Spray coupling: parcel_rhoTrans (species), parcel_UTrans (vector), parcel_UCoeff parcel_hsTrans parcel_hsCoeffByCp
+ *        (cells); no boundary counterparts (the spray block below). */
 int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long count, int layout);
 int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, int layout);
 
@@ -331,6 +333,60 @@ int dfmi_post_time_step(dfmi_ctx* ctx);         /* dfMatrixDataBase::postTimeSte
 int dfmi_time_step(dfmi_ctx* ctx, int n_corr);   /* non-zero also when chemistry hit its step limit */
 int dfmi_sync(dfmi_ctx* ctx);
 
+/* ---- spray coupling: the Lagrangian source terms parcels.Srho(rho) (rhoEqn.H:38), parcels.SU(U) (UEqn.H:9),
+ * parcels.SYi(i, Yi) (YEqn.H:110-111), parcels.Sh(he) and hcSource (EEqn.H:3-8, 27-28, 34-35). The cloud itself -- tracking,
+ * injection, break-up, evaporation, parcels.evolve() -- stays with the caller; this library takes the cloud's per-cell
+ * accumulators (already volume-integrated) and adds their terms to the four equations. No new entry point. Options:
+ *   spray.model  0 (default) | 1: the cloud's active && coupled
+ *   spray.rho, spray.U, spray.Yi, spray.h  0 explicit (default) | 1 semiImplicit   (sourceTerms.schemes of sprayCloudProperties)
+ * Fields (dfmi_set_field / dfmi_get_field, cells only, allocated zeroed at first use; values must be finite):
+ *   parcel_rhoTrans    [S][C]  kg      ReactingCloud::rhoTrans(i), every species, the inert one included
+ *   parcel_UTrans      [3][C]  kg m/s  KinematicCloud::UTrans()
+ *   parcel_UCoeff      [C]     kg      UCoeff(), not negative; read only with spray.U = 1
+ *   parcel_hsTrans     [C]     J       ThermoCloud::hsTrans()
+ *   parcel_hsCoeffByCp [C]     kg      hsCoeff() / thermo.Cp(), the quotient formed by the caller; read only with spray.h = 1
+ * They stay as set until written again: the caller sets them after parcels.evolve() (dfLowMachFoam.C:269-279) and before the
+ * step. With spray.model = 1 the terms below enter dfmi_rho_process, dfmi_U_process, dfmi_Y_process, dfmi_E_process,
+ * dfmi_assemble ("rho", "U", "Y", "Y_ell", "Y_ell_ref", "E"), what dfmi_get_matrix / dfmi_get_solver_rows then return, and
+ * dfmi_time_step -- every rhoEqn it runs, those of the pressure correctors included (pEqn.H:103 includes rhoEqn.H). The p
+ * equation gets no term (pEqn.H has none); dfmi_zero_d_step ignores the model.
+ * The statement below is the definition (KinematicCloudI.H:432-437, ThermoCloudI.H:236-245, ReactingCloudI.H:110-131 and
+ * 211-236, with A == T as A - T, fvm::Sp / fvm::SuSp as in the RAS block above, and a volume field added to a matrix as
+ * source -= V field). V the cell volume, rdt = 1 / deltaT as the ddt terms read it, rho / U / Yi / he the cell values as they
+ * stand when the equation is assembled (before its solve), hc_i = Hf298_i / W_i, the Qdot weights (CanteraMixture.H:325).
+ * Every operation is one fp64 rounding, evaluated left to right as written, no fused multiply-add; sums over species run
+ * i = 0 .. S-1 from 0.0:
+ *   rhoEqn    t = (sum_i rhoTrans_i) rdt
+ *     explicit      source = source + t
+ *     semiImplicit  a = (t / V) / rho;   diag = diag - V max(a, 0);   source = source + (V min(a, 0)) rho
+ *     then rho = source / diag (the diagonal solve); dfmi_assemble("rho") leaves this diag / source in dbg_rho_diag / _source
+ *   UEqn      per component k, into source and into source_solve (= source - grad p), hence into H and HbyA:
+ *     explicit      t_k = UTrans_k rdt
+ *     semiImplicit  diag = diag + UCoeff rdt;   t_k = (UTrans_k + UCoeff U_k) rdt
+ *                   rAU = 1 / ((diag + sum_slots (ic_0 + ic_1 + ic_2) / 3) / V) is formed again from this diag, so rAU,
+ *                   boundary_rAU and the p equation's rhorAUf carry it
+ *     source_k = source_k + t_k;   source_solve_k = source_solve_k + t_k
+ *   YEqn      every species i != inert (the inert species has no equation; its rhoTrans still counts in rho and hc):
+ *     explicit      source_i = source_i + rhoTrans_i rdt
+ *     semiImplicit  s = (rhoTrans_i rdt) / V;   s < 0:  diag_i = diag_i + (V (-s)) / (Y_i + 1e-15)      (OpenFOAM's small)
+ *                                               s >= 0: source_i = source_i + s V
+ *     the same in the hard-coded, species-chunked and LES / RAS forms of the assembly. In the solver rows the production
+ *     assembly writes ("Y_ell": dS = diag + sum internalCoeffs, rhs = source + boundaryCoeffs) the term is added to dS / rhs
+ *     after those sums; "Y_ell_ref" keeps that order, so the two stay equal bit for bit
+ *   EEqn      sens = hsTrans rdt
+ *     explicit      source = source + sens
+ *     semiImplicit  a = (hsCoeffByCp rdt) / V;   a >= 0: aV = a V;  diag = diag + aV;  source = source + (sens + aV he)
+ *                                                a <  0: source = source + sens   (the SuSp and the explicit echo cancel)
+ *     then, under either scheme, hcSource:  h = sum_i rhoTrans_i hc_i;   source = source + h rdt
+ * Each term is the last thing added to its equation's diag / source: under the "corrected" laplacian it comes after the
+ * explicit non-orthogonal term. So "the matrix with spray.model = 1 is the matrix with spray.model = 0, then the term" is exact.
+ * The U and E solver rows are folded from these LDU parts (dS = (diag + term) + sum internalCoeffs).
+ * Works with les.model, ras.model, tci.model, every chemistry mode, scheme and traversal order, and on decomposed meshes
+ * (the terms are rank-local: no halo). Refused by name: spray.model = 1 with fgm.model = 1 or with an equation of state set;
+ * a required field never set (parcel_UCoeff / parcel_hsCoeffByCp only under their semiImplicit scheme); a scheme value other
+ * than 0 / 1; non-finite values, a negative parcel_UCoeff, a wrong count. With spray.model = 0 nothing is launched and, in a
+ * context that never touches these options or fields, nothing allocated. */
+
 /* ---- adjustable time step: the first two lines of the time loop, dfLowMachFoam.C:261-262
  * (#include "compressibleCourantNo.H", #include "setDeltaT.H"). The reference GPU path has no counterpart: its
  * step is fixed at setup (createGPUSolver.H:152 "TODO: get deltaT from time API"). */
@@ -405,6 +461,7 @@ int dfmi_set_preconditioner(dfmi_ctx* ctx, const char* eqn, const char* name);
  * "tci.*" (model, mixing, chemistry, Cmix, fuel, oxidizer, CO2, H2, version, C1, C2, Cgamma, Ctau, exp1, exp2:
  * dfmi_combustion_correct below),
  * "fgm.*" (model, combustion, solveEnthalpy, flameletT, Sct, Sc, incompPref, TMin, TMax: the flareFGM block below),
+ * "spray.*" (model, rho, U, Yi, h: the spray block above),
  * "dnn.tuned_gemm", "step.courant" (1: dfmi_time_step queues the Courant-number kernel behind its last
  * kernel and posts the result to pinned memory for dfmi_courant_no; 0, the default: nothing added); keys and
  * defaults in INTEGRATION.md. Solver-structure keys must be set before the first solve; unknown keys fail. */
