@@ -113,7 +113,7 @@ struct Ctx {
                                        {"fgm.TMax", 5000.0}};
   // spray coupling (options spray.*): the keys and defaults of the HIP library, accepted and kept; spray.model = 1 is refused by name
   std::map<std::string, double> spray = {{"spray.model", 0}, {"spray.rho", 0}, {"spray.U", 0}, {"spray.Yi", 0}, {"spray.h", 0}};
-  struct Les { int model = 0; double Ck = 0.094, Ce = 1.048, Cw = 0.325, Prt = 1.0, Sct = 1.0; bool valid = false, have_delta = false; } les;
+  struct Les { int model = 0; double Ck = 0.094, Ce = 1.048, Cw = 0.325, Csg = 1.5, Prt = 1.0, Sct = 1.0; bool valid = false, have_delta = false; } les;
   bool step_courant = false;   // option step.courant: accepted for the callers that set it; the number is always computed on demand
   bool have_sizes = false, have_topo = false, have_geom = false, have_bgeom = false;
   std::vector<int> psize, pkind, cyc_nbr, own, nei, bfc, poff, slot_patch, prim, partner, dims, inert_v;
@@ -1306,8 +1306,10 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
     if (ctx && key && std::string(key).rfind("les.", 0) == 0) {
       Ctx::Les& q = ctx->x.les;
       const std::string k(key);
-      double* slot = k == "les.Ck" ? &q.Ck : k == "les.Ce" ? &q.Ce : k == "les.Cw" ? &q.Cw : k == "les.Prt" ? &q.Prt : k == "les.Sct" ? &q.Sct : nullptr;
+      double* slot = k == "les.Ck" ? &q.Ck : k == "les.Ce" ? &q.Ce : k == "les.Cw" ? &q.Cw : k == "les.Csg" ? &q.Csg : k == "les.Prt" ? &q.Prt : k == "les.Sct" ? &q.Sct : nullptr;
       if (k == "les.model") {
+        CHECK(value != 4.0, "les.model 4 (Sigma) is not available in CPU-A (the model is the HIP library's alone)");
+        CHECK(value != 5.0, "les.model 5 (dynamicSmagorinsky) is not available in CPU-A");
         CHECK(value == 0.0 || value == 1.0 || value == 2.0, "les.model must be 0 (laminar), 1 (Smagorinsky) or 2 (WALE)");
         if ((int)value != q.model) q.valid = false;
         q.model = (int)value;
@@ -1385,7 +1387,7 @@ int dfmi_get_option(dfmi_ctx* ctx, const char* key, double* value) {
       const Ctx::Les& q = ctx->x.les;
       const std::string k(key);
       if (k == "les.model") { *value = q.model; return; }
-      const double* slot = k == "les.Ck" ? &q.Ck : k == "les.Ce" ? &q.Ce : k == "les.Cw" ? &q.Cw : k == "les.Prt" ? &q.Prt : k == "les.Sct" ? &q.Sct : nullptr;
+      const double* slot = k == "les.Ck" ? &q.Ck : k == "les.Ce" ? &q.Ce : k == "les.Cw" ? &q.Cw : k == "les.Csg" ? &q.Csg : k == "les.Prt" ? &q.Prt : k == "les.Sct" ? &q.Sct : nullptr;
       CHECK(slot, "unknown option '" + k + "'");
       *value = *slot;
       return;

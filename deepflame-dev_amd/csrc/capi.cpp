@@ -87,12 +87,25 @@ void allocate_fields(Ctx& x) {
 // LES (options les.*): the filter width and the eddy viscosity dfmi_turbulence_correct forms. Allocated when the mode,
 // one of these fields or nut's patch types is first touched: a laminar context allocates what it always did, so its
 // buffers sit where they sat (the headline step is sensitive to that: profiles/les_ab.json)
+// dynamicSmagorinsky (les.model = 5) alone: S and its non-coupled slots, the two contractions with their halo slots, and
+// the get-only results. Allocated on the first use of model 5: every other context allocates what it always did.
+void ensure_dyn_fields(Ctx& x) {
+  if (x.les.model != 5 || x.fields.count("les_Cs")) return;
+  alloc_field(x, "les_S", x.C, 6, false);
+  alloc_field(x, "boundary_les_S", x.B, 6, true);
+  for (auto n : {"les_LLMM", "les_MMMM"}) {
+    alloc_field(x, n, x.C, 1, false);
+    alloc_field(x, std::string("boundary_") + n, x.B, 1, true);
+  }
+  for (auto n : {"les_Cs", "les_LM", "les_MM"}) alloc_field(x, n, x.C, 1, false);
+}
 void ensure_les_fields(Ctx& x) {
-  if (x.fields.count("nut")) return;
+  if (x.fields.count("nut")) { ensure_dyn_fields(x); return; }
   DFMI_CHECK(x.have_bgeom, "call dfmi_init_constant_fields_boundary first");
   alloc_field(x, "delta", x.C, 1, false);
   alloc_field(x, "nut", x.C, 1, false);
   alloc_field(x, "boundary_nut", x.B, 1, true);
+  ensure_dyn_fields(x);
 }
 
 // RAS k-epsilon (options ras.*): k, epsilon and their slots, the inletValue of both, G and divU, the solved (pre-bound)
@@ -1011,6 +1024,8 @@ int dfmi_set_field(dfmi_ctx* ctx, const char* name, const double* host, long cou
                "field '" + n + "' is formed by dfmi_turbulence_correct and cannot be set");
     DFMI_CHECK(n != "boundary_yPlus", "field 'boundary_yPlus' is formed by dfmi_turbulence_correct and cannot be set");
     DFMI_CHECK(n != "nut", "field 'nut' is formed by dfmi_turbulence_correct and cannot be set (boundary_nut holds the fixed-value slots)");
+    DFMI_CHECK(n.rfind("les_", 0) != 0 && n.rfind("boundary_les_", 0) != 0,
+               "field '" + n + "' is formed by dfmi_turbulence_correct (les.model = 5) and cannot be set");
     DFMI_CHECK(n.rfind("nonorth_", 0) != 0 && n.rfind("boundary_nonorth_", 0) != 0,
                "field '" + n + "' is formed by the library (dfmi_set_scheme \"laplacian\") and cannot be set");
     const int spi = spray_index(n);
@@ -1044,6 +1059,8 @@ int dfmi_get_field(dfmi_ctx* ctx, const char* name, double* host, long count, in
   return guard([&] {
     const std::string n(name ? name : "");
     if (n == "delta" || n == "nut" || n == "boundary_nut") ensure_les_fields(ctx->x);
+    if (n == "les_Cs" || n == "les_LM" || n == "les_MM")
+      DFMI_CHECK(ctx->x.fields.count(n), "field '" + n + "' exists with les.model = 5 (dynamicSmagorinsky) only");
     if (ras_name(n)) ensure_ras_fields(ctx->x);
     if (n == "rho_thermo" || n == "boundary_rho_thermo") ensure_eos_fields(ctx->x);
     if (fgm_name(n)) ensure_fgm_fields(ctx->x);
@@ -1731,8 +1748,9 @@ int dfmi_set_option(dfmi_ctx* ctx, const char* key, double value) {
                  "dfmi_set_option: p.n_nonorth (nNonOrthogonalCorrectors) must be an integer >= 0");
     if (k.rfind("les.", 0) == 0) {
       if (k == "les.model")
-        DFMI_CHECK(value == 0.0 || value == 1.0 || value == 2.0,
-                   "dfmi_set_option: les.model must be 0 (laminar), 1 (Smagorinsky) or 2 (WALE)");
+        DFMI_CHECK(value == 0.0 || value == 1.0 || value == 2.0 || value == 4.0 || value == 5.0,
+                   "dfmi_set_option: les.model must be 0 (laminar), 1 (Smagorinsky), 2 (WALE), 4 (Sigma) or 5 "
+                   "(dynamicSmagorinsky); 3 is reserved");
       else
         DFMI_CHECK(value > 0 && value <= 1.79769313486231570e308, "dfmi_set_option: " + k + " must be positive and finite");
       // nut belongs to the model and its coefficients (Prt and Sct enter the effective fields, formed at every

@@ -309,10 +309,12 @@ inline const OptDef* option_defs(int& n) {
                                       // main stream would wait for the side stream's YEqn rows (it reads what the U solve left)
     {"step.courant", 0},              // 1: dfmi_time_step ends with the Courant-number kernel and posts its record for
                                       // dfmi_courant_no (compressibleCourantNo.H, dfLowMachFoam.C:261); 0: nothing added
-    {"les.model", 0},                 // turbulence->: 0 laminar, 1 Smagorinsky, 2 WALE (LESeddyViscosity)
+    {"les.model", 0},                 // turbulence->: 0 laminar, 1 Smagorinsky, 2 WALE (LESeddyViscosity),
+                                      // 4 Sigma, 5 dynamicSmagorinsky (the reference's own); 3 is reserved and refused
     {"les.Ck", 0.094},                // nut = Ck delta sqrt(k) (both models)
     {"les.Ce", 1.048},                // Smagorinsky
     {"les.Cw", 0.325},                // WALE
+    {"les.Csg", 1.5},                 // Sigma: nut = (Csg delta)^2 Dsg (Sigma.C:84, default :118-126)
     {"les.Prt", 1.0},                 // alphaEff = alpha + mut / Prt (createFields.H:133)
     {"les.Sct", 1.0},                 // DEff_i = rhoD_i + mut / Sct
     {"ras.model", 0},                 // turbulence->: 0 none, 1 kEpsilon (RAS; include/dfmi.h)

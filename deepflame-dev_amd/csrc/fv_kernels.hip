@@ -967,6 +967,202 @@ __global__ void __launch_bounds__(TPB) k_les_nut(MeshView m, const int8_t* __res
   grad_u_cell<WT>(m, ty, U, bU, c, g);
   nut[c] = les_nut(q, g, delta[c]);
 }
+// Sigma (the reference's Sigma.C:40-89; Nicoud et al. 2011), les.model = 4, a kernel of its own so that k_les_nut keeps
+// its code: with the singular values s1 >= s2 >= s3 >= 0 of g,
+//   Dsg = s3 (s1 - s2)(s2 - s3) / (s1^2 + 1e-300),  nut = (Csg delta)^2 Dsg
+// The singular values come from one-sided (Hestenes) Jacobi on the columns of g in registers: g^T g is never formed and
+// there is no acos, because the closed form from the invariants loses seven digits wherever two singular values meet
+// or s3 is small -- the model's own zeros. One rotation of the columns p, q:
+//   a = p.p, b = q.q, c = p.q;  c == 0: identity (g = 0, rank 1 and orthogonal columns come out exact);
+//   z = (b - a) / (2 c), t = sign(z) / (|z| + sqrt(1 + z^2)), cs = 1 / sqrt(1 + t^2), sn = cs t,
+//   p' = cs p - sn q, q' = sn p + cs q
+// SIGMA_SWEEPS cyclic sweeps over (0,1), (0,2), (1,2), a fixed count: the fp64 restatement reaches rounding level
+// (<= 1.5e-16 of s1 in Dsg) in 4 sweeps on every state class of tests/sgs_reference.py; 3 sweeps leave 2.0e-7 where s3
+// is 1e-9 s1, 3.8e-7 where it is 0 and 1.6e-9 on random g (tests/golden/sgs_bounds.json "sweeps";
+// tests/test_sgs_cpu.py); 4 plus one of margin.
+constexpr int SIGMA_SWEEPS = 5;
+__device__ __forceinline__ void sigma_rotate(double (&p)[3], double (&q)[3]) {
+  const double a = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
+  const double b = q[0] * q[0] + q[1] * q[1] + q[2] * q[2];
+  const double c = p[0] * q[0] + p[1] * q[1] + p[2] * q[2];
+  if (c == 0.0) return;
+  const double z = (b - a) / (2.0 * c);
+  const double t = copysign(1.0, z) / (fabs(z) + sqrt(1.0 + z * z));
+  const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double pi = p[i], qi = q[i];
+    p[i] = cs * pi - sn * qi;
+    q[i] = sn * pi + cs * qi;
+  }
+}
+__device__ __forceinline__ double sigma_nut(double Csg, const double (&g)[9], double del) {
+  double c0[3] = {g[0], g[3], g[6]}, c1[3] = {g[1], g[4], g[7]}, c2[3] = {g[2], g[5], g[8]};   // the columns of g
+  for (int s = 0; s < SIGMA_SWEEPS; ++s) {
+    sigma_rotate(c0, c1);
+    sigma_rotate(c0, c2);
+    sigma_rotate(c1, c2);
+  }
+  const double n0 = sqrt(c0[0] * c0[0] + c0[1] * c0[1] + c0[2] * c0[2]);
+  const double n1 = sqrt(c1[0] * c1[0] + c1[1] * c1[1] + c1[2] * c1[2]);
+  const double n2 = sqrt(c2[0] * c2[0] + c2[1] * c2[1] + c2[2] * c2[2]);
+  const double s1 = fmax(n0, fmax(n1, n2)), s3 = fmin(n0, fmin(n1, n2));
+  const double s2 = fmax(fmin(n0, n1), fmin(fmax(n0, n1), n2));   // the true middle value
+  const double Dsg = s3 * (s1 - s2) * (s2 - s3) / (s1 * s1 + 1e-300);
+  const double cd = Csg * del;
+  return cd * cd * Dsg;
+}
+// k_les_nut's gather, then the rotations in registers; 8 B out
+template <int WT>
+__global__ void __launch_bounds__(TPB) k_les_sigma(MeshView m, const int8_t* __restrict__ ty, const double* __restrict__ U,
+                                                   const double* __restrict__ bU, const double* __restrict__ delta,
+                                                   double Csg, double* __restrict__ nut) {
+  const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
+  if (c >= m.C) return;
+  double g[9];
+  grad_u_cell<WT>(m, ty, U, bU, c, g);
+  nut[c] = sigma_nut(Csg, g, delta[c]);
+}
+// dynamicSmagorinsky (the reference's dynamicSmagorinsky.C:38-49, 141-199), les.model = 5: the statement in
+// include/dfmi.h is the definition. Three per-cell gathers around one test filter.
+//
+// The filter (simpleFilter / fvc::average): F(x)_c = sum_f |Sf| x_f / sum_f |Sf| over the cell's faces in the sequential
+// order, then its primary non-empty slots; x_f linear on internal and coupled faces, the slot's value elsewhere. N
+// quantities at once, one accumulator each. It names none of its operands: cell(c, v) gives the N values of a cell,
+// slot(b, t, own, v) those of boundary slot b of type t (a non-coupled slot's boundary values, or, on a processor
+// slot, the neighbour cell's from the halo).
+template <int WT, int N, class CELL, class SLOT>
+__device__ __forceinline__ void les_filter(const MeshView& m, const int8_t* __restrict__ ty, int c, CELL&& cell, SLOT&& slot,
+                                           double (&out)[N]) {
+  double own[N], s[N], A = 0.0;
+  cell(c, own);
+#pragma unroll
+  for (int k = 0; k < N; ++k) s[k] = 0.0;
+  each_face<WT>(m, c, [&](int f, int o2, bool isown) {
+    const double w = m.w[f], a = m.magSf[f];
+    double nb[N];
+    cell(o2, nb);
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k] += a * (isown ? interp_f(w, own[k], nb[k]) : interp_f(w, nb[k], own[k]));
+    A += a;
+  });
+  each_slot(m, ty, c, [&](int b, int t) {
+    const double a = m.bmagSf[b];
+    double xb[N];
+    if (bc_coupled(t)) {
+      const int pc = m.partner[b];
+      if (pc >= 0) cell(pc, xb); else slot(b, t, own, xb);
+      const double w = m.bw[b];
+#pragma unroll
+      for (int k = 0; k < N; ++k) xb[k] = interp_b(w, own[k], xb[k]);
+    } else slot(b, t, own, xb);
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k] += a * xb[k];
+    A += a;
+  });
+#pragma unroll
+  for (int k = 0; k < N; ++k) out[k] = s[k] / A;
+}
+// S = dev(symm(g)) as (xx, xy, xz, yy, yz, zz); && of two symmetric tensors in that storage
+__device__ __forceinline__ void dev_symm(const double (&g)[9], double (&S)[6]) {
+  const double t3 = (1.0 / 3.0) * (g[0] + g[4] + g[8]);
+  S[0] = g[0] - t3; S[1] = 0.5 * (g[1] + g[3]); S[2] = 0.5 * (g[2] + g[6]);
+  S[3] = g[4] - t3; S[4] = 0.5 * (g[5] + g[7]); S[5] = g[8] - t3;
+}
+__device__ __forceinline__ double sym_dd(const double* a, const double* b) {
+  return (a[0] * b[0] + a[3] * b[3] + a[5] * b[5]) + 2.0 * (a[1] * b[1] + a[2] * b[2] + a[4] * b[4]);
+}
+// pass 1: g -> S on the cell and, from the boundary gradient k_u_grad forms (g_c + n (snGrad - n . g_c)), on its
+// non-coupled slots
+template <int WT>
+__global__ void __launch_bounds__(TPB) k_dyn_strain(MeshView m, const int8_t* __restrict__ ty, const double* __restrict__ U,
+                                                    const double* __restrict__ bU, double* __restrict__ S, double* __restrict__ bS) {
+  const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
+  if (c >= m.C) return;
+  const long C = m.C, B = m.B;
+  double g[9], s[6];
+  grad_u_cell<WT>(m, ty, U, bU, c, g);
+  dev_symm(g, s);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) S[k * C + c] = s[k];
+  each_slot(m, ty, c, [&](int b, int t) {
+    if (bc_coupled(t)) return;
+    const double ms = m.bmagSf[b];
+    const double nv[3] = {m.bSf[b] / ms, m.bSf[B + b] / ms, m.bSf[2 * B + b] / ms};
+    double bg[9], bs[6];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double sn = (t == FIXED_VALUE || bc_mixed(t)) ? m.bdc[b] * (bU[j * B + b] - U[j * C + c]) : 0.0;
+      const double corr = sn - (nv[0] * g[0 * 3 + j] + nv[1] * g[1 * 3 + j] + nv[2] * g[2 * 3 + j]);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) bg[i * 3 + j] = g[i * 3 + j] + nv[i] * corr;
+    }
+    dev_symm(bg, bs);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) bS[k * B + b] = bs[k];
+  });
+}
+// the 21 filtered quantities of pass 2 from a point's U (3) and S (6): U, U U (6), S, |S| S. Products are formed
+// per point (cell or slot), then interpolated.
+__device__ __forceinline__ void dyn_point(const double* __restrict__ U, const double* __restrict__ S, long n, long i, double* v) {
+  const double u0 = U[i], u1 = U[n + i], u2 = U[2 * n + i];
+  double s[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) s[k] = S[k * n + i];
+  const double ms = sqrt(sym_dd(s, s));
+  v[0] = u0; v[1] = u1; v[2] = u2;
+  v[3] = u0 * u0; v[4] = u0 * u1; v[5] = u0 * u2; v[6] = u1 * u1; v[7] = u1 * u2; v[8] = u2 * u2;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { v[9 + k] = s[k]; v[15 + k] = ms * s[k]; }
+}
+// pass 2: LL = dev(F(U U) - F(U) F(U)), MM = delta^2 (F(|S| S) - 4 |F(S)| F(S)); out LL && MM and MM && MM
+template <int WT>
+__global__ void __launch_bounds__(TPB) k_dyn_filter(MeshView m, const int8_t* __restrict__ ty, const double* __restrict__ U,
+                                                    const double* __restrict__ bU, const double* __restrict__ S,
+                                                    const double* __restrict__ bS, const double* __restrict__ delta,
+                                                    double* __restrict__ llmm, double* __restrict__ mmmm) {
+  const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
+  if (c >= m.C) return;
+  const long C = m.C, B = m.B;
+  double F[21];
+  les_filter<WT, 21>(m, ty, c, [&](int o, double* v) { dyn_point(U, S, C, o, v); },
+                     [&](int b, int, const double*, double* v) { dyn_point(bU, bS, B, b, v); }, F);
+  double LL[6], MM[6];
+  LL[0] = F[3] - F[0] * F[0]; LL[1] = F[4] - F[0] * F[1]; LL[2] = F[5] - F[0] * F[2];
+  LL[3] = F[6] - F[1] * F[1]; LL[4] = F[7] - F[1] * F[2]; LL[5] = F[8] - F[2] * F[2];
+  const double t3 = (1.0 / 3.0) * (LL[0] + LL[3] + LL[5]);
+  LL[0] -= t3; LL[3] -= t3; LL[5] -= t3;
+  const double mfs = sqrt(sym_dd(F + 9, F + 9)), d2 = delta[c] * delta[c];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) MM[k] = d2 * (F[15 + k] - 4.0 * mfs * F[9 + k]);
+  llmm[c] = sym_dd(LL, MM);
+  mmmm[c] = sym_dd(MM, MM);
+}
+// pass 3: LM = F(LL && MM), MMMM = max(F(MM && MM), 1e-300) (a non-coupled slot carries the cell's own value:
+// surfaceSum returns an extrapolated field), Cs = 0.5 LM / MMMM, nut = max(Cs delta^2 |S|, -mu / rho)
+template <int WT>
+__global__ void __launch_bounds__(TPB) k_dyn_nut(MeshView m, const int8_t* __restrict__ ty, const double* __restrict__ llmm,
+                                                 const double* __restrict__ bllmm, const double* __restrict__ mmmm,
+                                                 const double* __restrict__ bmmmm, const double* __restrict__ S,
+                                                 const double* __restrict__ delta, const double* __restrict__ mu,
+                                                 const double* __restrict__ rho, double* __restrict__ LM, double* __restrict__ MMo,
+                                                 double* __restrict__ Cs, double* __restrict__ nut) {
+  const int c = cell_of(m, xcd_block() * blockDim.x + threadIdx.x);
+  if (c >= m.C) return;
+  const long C = m.C;
+  double F[2];
+  les_filter<WT, 2>(m, ty, c, [&](int o, double* v) { v[0] = llmm[o]; v[1] = mmmm[o]; },
+                    [&](int b, int t, const double* own, double* v) {
+                      if (bc_coupled(t)) { v[0] = bllmm[b]; v[1] = bmmmm[b]; } else { v[0] = own[0]; v[1] = own[1]; }
+                    }, F);
+  const double mm = fmax(F[1], 1e-300), cs = 0.5 * F[0] / mm;
+  double s[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) s[k] = S[k * C + c];
+  const double d = delta[c];
+  LM[c] = F[0]; MMo[c] = mm; Cs[c] = cs;
+  nut[c] = fmax(cs * (d * d) * sqrt(sym_dd(s, s)), -mu[c] / rho[c]);
+}
 // mut = rho nut; muEff = mut + mu; alphaEff = alpha + mut / Prt; mutSct = mut / Sct (in this order, no contraction),
 // over n cells or n boundary slots (each slot from its own boundary values)
 __global__ void k_les_effective(long n, const double* __restrict__ rho, const double* __restrict__ nut,
@@ -3009,8 +3205,22 @@ void u_hbya(Ctx& x) {
 void turbulence_correct(Ctx& x) {
   if (!x.les.model) return;
   DFMI_CHECK(x.les.have_delta, "LES: the filter width field 'delta' is not set (dfmi_set_field)");
-  const LesCoef q{x.les.model, x.opt("les.Ck"), x.opt("les.Ce"), x.opt("les.Cw")};
-  LAUNCH_W(k_les_nut, x.C, x.view(), x.st("U"), x.f("U"), x.f("boundary_U"), x.f("delta"), q, x.f("nut"));
+  if (x.les.model == 5) {
+    // S, then the two contractions, then nut travel through the halo; mu and rho as the context holds them
+    LAUNCH_W(k_dyn_strain, x.C, x.view(), x.st("U"), x.f("U"), x.f("boundary_U"), x.f("les_S"), x.f("boundary_les_S"));
+    halo_fields(x, {"les_S"});
+    LAUNCH_W(k_dyn_filter, x.C, x.view(), x.st("U"), x.f("U"), x.f("boundary_U"), x.f("les_S"), x.f("boundary_les_S"),
+             x.f("delta"), x.f("les_LLMM"), x.f("les_MMMM"));
+    halo_fields(x, {"les_LLMM", "les_MMMM"});
+    LAUNCH_W(k_dyn_nut, x.C, x.view(), x.st("U"), x.f("les_LLMM"), x.f("boundary_les_LLMM"), x.f("les_MMMM"),
+             x.f("boundary_les_MMMM"), x.f("les_S"), x.f("delta"), x.f("mu"), x.f("rho"), x.f("les_LM"), x.f("les_MM"),
+             x.f("les_Cs"), x.f("nut"));
+  } else if (x.les.model == 4) {
+    LAUNCH_W(k_les_sigma, x.C, x.view(), x.st("U"), x.f("U"), x.f("boundary_U"), x.f("delta"), x.opt("les.Csg"), x.f("nut"));
+  } else {
+    const LesCoef q{x.les.model, x.opt("les.Ck"), x.opt("les.Ce"), x.opt("les.Cw")};
+    LAUNCH_W(k_les_nut, x.C, x.view(), x.st("U"), x.f("U"), x.f("boundary_U"), x.f("delta"), q, x.f("nut"));
+  }
   k_bc_correct(x, x.stype.count("nut") ? "nut" : "calculated", x.f("nut"), x.f("boundary_nut"), 1);
   halo_fields(x, {"nut"});
   x.les.valid = true;

@@ -5,11 +5,15 @@ The eddy viscosity itself is formed on the device. This module reads a case's co
 from the chemistry dictionary, createFields.H:133), computes the filter width `delta` on the host as OpenFOAM-7's
 cubeRootVolDelta does, and sets the options and fields of a context.
 
-Supported: simulationType laminar | LES; LESModel Smagorinsky | WALE; delta cubeRootVol. Everything else (the
-dynamic models, Sigma, the other delta types) is refused by name: DESIGN.md 10. parse_turbulence_properties reads the
-laminar and LES files and refuses RAS; parse_ras_properties reads simulationType RAS with RASModel kEpsilon (DESIGN.md
-14) and refuses RNGkEpsilon, every other RASModel and `turbulence off` by name; read_case_turbulence reads
-simulationType and hands the file to one or the other.
+Supported: simulationType laminar | LES; LESModel Smagorinsky | WALE (OpenFOAM-7) | Sigma |
+dynamicSmagorinsky with `filter simple` (the reference's own, src/TurbulenceModels/turbulenceModels); delta
+cubeRootVol. Everything else (dynamicKEqn, dynamicLagrangian and every other LESModel, the `laplace` and `anisotropic`
+filters, the other delta types) is refused by name: DESIGN.md 10. parse_turbulence_properties reads the laminar and the
+OpenFOAM-7 LES files and refuses Sigma, dynamicSmagorinsky and RAS; parse_les_properties reads those, `LESModel Sigma` with `SigmaCoeffs { Csg }`
+and `LESModel dynamicSmagorinsky` with `dynamicSmagorinskyCoeffs { filter simple; }`, and returns the same dictionary plus
+"Csg" and "filter"; parse_ras_properties reads simulationType RAS with RASModel kEpsilon
+ and refuses RNGkEpsilon, every other RASModel and `turbulence off` by name; read_case_turbulence reads
+simulationType and hands laminar and LES files to parse_les_properties, RAS files to parse_ras_properties.
 """
 from __future__ import annotations
 
@@ -23,6 +27,12 @@ MODELS = {"Smagorinsky": 1, "WALE": 2}
 # OpenFOAM-7 defaults (LESeddyViscosity: Ce 1.048; Smagorinsky / WALE: Ck 0.094; WALE: Cw 0.325), Prt = Sct = 1
 DEFAULTS = {"Ck": 0.094, "Ce": 1.048, "Cw": 0.325, "Prt": 1.0, "Sct": 1.0, "deltaCoeff": 1.0}
 _COEFFS = {"Smagorinsky": ("Ck", "Ce"), "WALE": ("Ck", "Ce", "Cw")}
+# parse_les_properties: the reference's Sigma beside them (Csg 1.5, Sigma.C:118-126; it is an LESeddyViscosity, whose Ce
+# it reads and never uses)
+LES_MODELS = dict(MODELS, Sigma=4, dynamicSmagorinsky=5)
+_LES_COEFFS = dict(_COEFFS, Sigma=("Csg", "Ce"), dynamicSmagorinsky=("Ce", "filter"))
+FILTERS = ("simple",)          # `laplace` and `anisotropic` are refused by name
+CSG_DEFAULT = 1.5
 
 
 def _strip(txt: str) -> str:
@@ -67,6 +77,23 @@ def parse_turbulence_properties(txt: str, chemistry_txt: str | None = None) -> d
     """{"model": 0 | 1 | 2, "LESModel": name | None, "Ck", "Ce", "Cw", "Prt", "Sct", "deltaCoeff"} from the text of
     constant/turbulenceProperties and, for Sct, of the chemistry dictionary (CanteraTorchProperties). The last entry of a
     keyword wins; coefficients not given take OpenFOAM-7's defaults."""
+    return _parse_les(txt, chemistry_txt, MODELS, _COEFFS)
+
+
+def parse_les_properties(txt: str, chemistry_txt: str | None = None) -> dict:
+    """parse_turbulence_properties' dictionary plus "Csg" and "filter" (None unless the model has a test filter),
+    with `LESModel Sigma` and `SigmaCoeffs { Csg }` accepted beside Smagorinsky and WALE ("model": 4), and
+    `LESModel dynamicSmagorinsky` with `dynamicSmagorinskyCoeffs { filter simple; }` ("model": 5, "filter": "simple").
+    Every other model, filter, delta type and unknown coefficient is refused by name."""
+    out = _parse_les(txt, chemistry_txt, LES_MODELS, _LES_COEFFS)
+    out.setdefault("Csg", CSG_DEFAULT)
+    out.setdefault("filter", None)
+    if out["model"] == 5 and out["filter"] is None:
+        raise ValueError("turbulenceProperties: dynamicSmagorinskyCoeffs has no filter entry (simple)")
+    return out
+
+
+def _parse_les(txt: str, chemistry_txt: str | None, MODELS: dict, _COEFFS: dict) -> dict:
     txt = _strip(txt)
     top = dict(dict_entries(txt))
     sim = top.get("simulationType")
@@ -102,7 +129,11 @@ def parse_turbulence_properties(txt: str, chemistry_txt: str | None = None) -> d
         out["Prt"] = _number("turbulenceProperties LES", "Prt", ent["Prt"])
     coeffs = sub_dict(les, name + "Coeffs")
     for k, v in dict_entries(coeffs or ""):
-        if k in _COEFFS[name] or k == "Prt":
+        if k == "filter" and k in _COEFFS[name]:
+            if v not in FILTERS:
+                raise ValueError(f"turbulenceProperties: {name}Coeffs filter {v} is not supported ({', '.join(FILTERS)})")
+            out["filter"] = v
+        elif k in _COEFFS[name] or k == "Prt":
             out[k] = _number(f"turbulenceProperties {name}Coeffs", k, v)
         else:
             raise ValueError(f"turbulenceProperties: {name}Coeffs entry {k} is not supported ({', '.join(_COEFFS[name])})")
@@ -159,12 +190,15 @@ def cube_root_vol_delta(m, delta_coeff: float = 1.0, thickness: float | None = N
 
 def apply(ctx, m, settings: dict, nut_patch_types=None) -> None:
     """the options les.*, the field delta and (if given) nut's patch types on a context that has been set up
-    (case.setup_context). settings: parse_turbulence_properties' result. Laminar: only les.model = 0 is set."""
+    (case.setup_context). settings: parse_turbulence_properties' or parse_les_properties' result. Laminar: only
+    les.model = 0 is set. Sigma (model 4): les.Csg too."""
     ctx.set_option("les.model", settings["model"])
     if not settings["model"]:
         return
     for k in ("Ck", "Ce", "Cw", "Prt", "Sct"):
         ctx.set_option("les." + k, settings[k])
+    if settings["model"] == 4:
+        ctx.set_option("les.Csg", settings.get("Csg", CSG_DEFAULT))
     if nut_patch_types is not None:
         ctx.set_patch_types("nut", nut_patch_types)
     ctx.set_field("delta", cube_root_vol_delta(m, settings["deltaCoeff"]))
@@ -232,14 +266,25 @@ def read_ras_properties(path: str, chemistry_path: str | None = None) -> dict:
     return parse_ras_properties(txt, chem)
 
 
+def read_les_properties(path: str, chemistry_path: str | None = None) -> dict:
+    """parse_les_properties of a case's constant/turbulenceProperties (and chemistry dictionary)"""
+    with open(path) as f:
+        txt = f.read()
+    chem = None
+    if chemistry_path is not None:
+        with open(chemistry_path) as f:
+            chem = f.read()
+    return parse_les_properties(txt, chem)
+
+
 def read_case_turbulence(path: str, chemistry_path: str | None = None) -> dict:
     """the settings of a case's constant/turbulenceProperties whatever its simulationType: laminar and LES through
-    read_turbulence_properties, RAS through read_ras_properties (its result has "RASModel")"""
+    read_les_properties, RAS through read_ras_properties (its result has "RASModel")"""
     with open(path) as f:
         sim = dict(dict_entries(_strip(f.read()))).get("simulationType")
     if sim == "RAS":
         return read_ras_properties(path, chemistry_path)
-    return read_turbulence_properties(path, chemistry_path)
+    return read_les_properties(path, chemistry_path)
 
 
 def apply_ras(ctx, m, settings: dict, patch_types: dict | None = None, k=None, epsilon=None, patch_params: dict | None = None) -> None:

@@ -198,7 +198,8 @@ int dfmi_thermo_set_eos(dfmi_ctx* ctx, int model, int num_species, const double*
  *        boundary_<name> for the boundary counterparts; boundary-only: boundary_heGradient,
  *        boundary_{U,p,Y,K}_ref (inletOutlet inletValue), boundary_p_vf (waveTransmissive valueFraction),
  *        boundary_p_gamma, chem_stats [3][C]. count = values per component.
- *        LES: delta (cells; positive), nut (cells; get only), boundary_nut (set: the fixedValue / calculated slots).
+ *        LES: delta (cells; positive), nut (cells; get only), boundary_nut (set: the fixedValue / calculated slots);
+ *        les.model = 5, get only: les_Cs les_LM les_MM (cells).
  *        RAS: k epsilon (cells), boundary_{k,epsilon}, boundary_{k,epsilon}_ref; get only: G divU k_prebound epsilon_prebound,
  *        boundary_yPlus (the nutkWallFunction slots' yPlus, zero elsewhere).
  *        Combustion closure: tci_tc (cells); get only: tci_kappa tci_tmix tci_tauStar Qdot_eff (cells), RR_eff (species).
@@ -218,12 +219,43 @@ int dfmi_E_process(dfmi_ctx* ctx);              /* dfEEqn::process (dfEEqn.cu:10
 /* ---- LES eddy viscosity: turbulence->correct() (dfLowMachFoam.C:508). Every equation of the reference goes through
  * turbulence-> (UEqn.H:6 divDevRhoReff(U); YEqn.H:96 DEff = rhoD(i) + mut/Sct; EEqn.H:20-37 laplacian(alphaEff, he));
  * its GPU path carries a Smagorinsky kernel it never calls (src_gpu/dfUEqn.cu:305-353). Options (dfmi_set_option):
- *   les.model  0 laminar (default) | 1 Smagorinsky | 2 WALE (OpenFOAM-7 LESeddyViscosity; anything else is refused)
- *   les.Ck 0.094, les.Ce 1.048 (Smagorinsky), les.Cw 0.325 (WALE), les.Prt 1, les.Sct 1 (createFields.H:133)
+ *   les.model  0 laminar (default) | 1 Smagorinsky | 2 WALE (OpenFOAM-7 LESeddyViscosity) | 4 Sigma | 5 dynamicSmagorinsky
+ *              (the reference's own src/TurbulenceModels/turbulenceModels/Sigma/Sigma.C and
+ *              dynamicSmagorinsky/dynamicSmagorinsky.C). 3 is reserved and refused; anything else is refused
+ *   les.Ck 0.094, les.Ce 1.048 (Smagorinsky), les.Cw 0.325 (WALE), les.Csg 1.5 (Sigma, Sigma.C:118-126), les.Prt 1,
+ *   les.Sct 1 (createFields.H:133)
  * With g = grad(U) (the UEqn's Gauss linear gradient), D = symm(g) and the field "delta":
  *   Smagorinsky  a = Ce/delta, b = (2/3) tr D, c = 2 Ck delta (dev(D) && D), k = ((-b + sqrt(b^2 + 4ac)) / (2a))^2
  *   WALE         Sd = dev(symm(g.g)), m = Sd && Sd, s = D && D, k = (Cw^2 delta/Ck)^2 m^3 / ((s^(5/2) + m^(5/4))^2 + 1e-15)
  *   nut = Ck delta sqrt(k); boundary_nut = nut.correctBoundaryConditions() by the patch types of "nut".
+ *   Sigma (Sigma.C:40-89), with the singular values s1 >= s2 >= s3 >= 0 of g:
+ *                Dsg = s3 (s1 - s2)(s2 - s3) / (s1^2 + 1e-300), nut = (Csg delta)^2 Dsg
+ *     s2 is the true middle singular value. The reference's loop (Sigma.C:64-66) keeps the last value OpenFOAM's unsorted
+ *     SVD returns, whichever it is, so its Dsg is zero whenever that is the largest or the smallest: a deliberate deviation
+ *     (DESIGN.md 9). The singular values are the column norms of g after 5 cyclic sweeps of one-sided (Hestenes) Jacobi
+ *     rotations on the columns of g over the pairs (0,1), (0,2), (1,2): a = p.p, b = q.q, c = p.q; c == 0 is the identity;
+ *     else z = (b - a) / (2c), t = sign(z) / (|z| + sqrt(1 + z^2)), cs = 1 / sqrt(1 + t^2), sn = cs t, p' = cs p - sn q,
+ *     q' = sn p + cs q. g^T g is never formed. g = 0, a rank-1 g and a g with orthogonal columns give nut = 0 exactly.
+ *   dynamicSmagorinsky (dynamicSmagorinsky.C:38-49, 141-199; `filter simple` only). OpenFOAM-7's simpleFilter, fvc::average
+ *   and surfaceSum are restated here, and this statement is the definition:
+ *     The filter  F(x)_c = sum_f |Sf| x_f / sum_f |Sf| over every face of cell c that carries an internal face or a
+ *       boundary slot (`empty` faces carry neither), the cell's internal faces in the sequential order, then its slots.
+ *       x_f = w x_P + (1 - w) x_N on internal and coupled faces (cyclic: the partner cell; processor: the neighbour cell's
+ *       value from the halo). On a non-coupled slot x_f is the field's boundary value: boundary_U for U; for a product the
+ *       product of the boundary values; for S the value formed from the boundary gradient the UEqn forms,
+ *       g_b = g_c + n (snGrad - n . g_c) with snGrad = deltaCoeffs (boundary_U - U_c) on fixedValue and mixed slots, 0
+ *       elsewhere; for LL && MM and MM && MM the cell's own value (surfaceSum returns an extrapolated field).
+ *       fvc::average of a cell field is the same operator. The boundary value of delta is never read (MM multiplies by
+ *       the cell's delta after the filter).
+ *     S = dev(symm(g)), |S| = sqrt(S && S);  LL = dev(F(U U) - F(U) F(U));  MM = delta^2 (F(|S| S) - 4 |F(S)| F(S))
+ *     les_LM = F(LL && MM);  les_MM = max(F(MM && MM), 1e-300);  les_Cs = 0.5 les_LM / les_MM
+ *     nut = max(les_Cs delta^2 |S|, -mu / rho), mu and rho as the context holds them at the call
+ *     les_Cs and nut take both signs ("to allow for backscatter"). les_Cs, les_LM, les_MM are get-only cell fields that
+ *     exist from the first use of les.model = 5. Three kernels (S on cells and non-coupled slots; the four filtered
+ *     quantities and the two contractions; their average, Cs and nut); several ranks: S, then the two contractions, then
+ *     nut cross the processor patches.
+ *     Everything downstream of nut (the validity rule, boundary_nut, the halo, the three assemblies, the refusals together
+ *     with ras.model, tci.model, fgm.model, an equation of state and spray) is as for models 1 and 2.
  * This call forms nut and boundary_nut from U / boundary_U as they stand (several ranks: a collective, the processor
  * slots' neighbour half is exchanged). dfmi_time_step runs it after the last pressure corrector, and first thing when
  * nut is not valid (turbulence->validate(), dfLowMachFoam.C:207): after les.model or a coefficient changed, "delta"

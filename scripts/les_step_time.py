@@ -2,7 +2,8 @@
 """Step time of the headline workload in LES mode beside the laminar step.
 
 The bench.py headline state (128^3 box, Burke 9 species, ODE chemistry, the case's schemes), one context per arm:
-les.model = 0 (laminar), 1 (Smagorinsky), 2 (WALE); delta = cubeRootVol. Per arm: warm-up steps, timed steps (median
+les.model = 0 (laminar), 1 (Smagorinsky), 2 (WALE), 4 (Sigma: k_les_sigma), 5 (dynamicSmagorinsky: k_dyn_strain, k_dyn_filter,
+k_dyn_nut); delta = cubeRootVol. Per arm: warm-up steps, timed steps (median
 of the per-step HIP events, dfmi_step_timer), then a few steps with dfmi_kernel_timer armed on the eddy-viscosity
 kernel and the YEqn preparation, and the kernel's algorithmic bytes and share of the 8 TB/s bound. The arms alternate
 ROUNDS times. Writes one JSON document (argument: output path; default stdout)."""
@@ -23,6 +24,16 @@ def nut_bytes(C, F, Bc, hex_walk):
     topology k_u_grad counts (bench.py algorithmic_bytes)"""
     topo = (4.0 * C + 9.0 * Bc) if hex_walk else (12.0 * C + 12.0 * F + 9.0 * Bc)
     return C * (24.0 + 16.0 + 8.0) + F * 32.0 + Bc * 32.0 + topo
+
+
+def dyn_bytes(C, F, Bc, hex_walk):
+    """the three dynamicSmagorinsky passes, each input and output once. strain: k_les_nut's gather without delta, S (6)
+    out; filter: U (3), S (6), delta in and the two contractions out per cell, w and |Sf| per face and coupled slot;
+    nut: the two contractions, S (6), delta, mu, rho in and LM, MM, Cs, nut out per cell, w and |Sf| per face"""
+    topo = (4.0 * C + 9.0 * Bc) if hex_walk else (12.0 * C + 12.0 * F + 9.0 * Bc)
+    return {"k_dyn_strain": C * (24.0 + 8.0 + 48.0) + F * 32.0 + Bc * 32.0 + topo,
+            "k_dyn_filter": C * (72.0 + 8.0 + 16.0) + F * 16.0 + Bc * 16.0 + topo,
+            "k_dyn_nut": C * (16.0 + 48.0 + 24.0 + 32.0) + F * 16.0 + Bc * 16.0 + topo}
 
 
 def main():
@@ -49,7 +60,7 @@ def main():
     f = bench.reference_fields(m, ym["species"])
     mech = parse_mechanism(os.path.join(golden, yml))
     Bc = sum(p.size for p in m.patches if p.kind in ("cyclic", "processor", "processorCyclic"))
-    names = {0: "laminar", 1: "Smagorinsky", 2: "WALE"}
+    names = {0: "laminar", 1: "Smagorinsky", 2: "WALE", 4: "Sigma", 5: "dynamicSmagorinsky"}
     runs = {n: [] for n in names.values()}
     kern = {}
     for rnd in range(args.rounds):
@@ -71,10 +82,11 @@ def main():
             ctx.step_timer(False)
             runs[name].append({"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max())})
             if rnd == 0:
-                ctx.kernel_timer("k_les_nut,k_y_prep,k_les_effective,k_u_grad")
+                ctx.kernel_timer("k_les_nut,k_les_sigma,k_dyn_strain,k_dyn_filter,k_dyn_nut,k_y_prep,k_les_effective,k_u_grad")
                 for _ in range(args.kernel_steps):
                     ctx.time_step(2)
-                k = {kn: ctx.kernel_time(kn) for kn in ("k_les_nut", "k_y_prep", "k_les_effective", "k_u_grad")}
+                k = {kn: ctx.kernel_time(kn) for kn in ("k_les_nut", "k_les_sigma", "k_dyn_strain", "k_dyn_filter", "k_dyn_nut", "k_y_prep",
+                                                         "k_les_effective", "k_u_grad")}
                 ctx.kernel_timer("")
                 kern[name] = {kn: {"launches": v[1], "us_per_launch": (1e3 * v[0] / v[1]) if v[1] else None} for kn, v in k.items()}
                 if model:
@@ -82,6 +94,7 @@ def main():
                     mu = ctx.get_field("mu", (m.n_cells,))
                     rho = ctx.get_field("rho", (m.n_cells,))
                     kern[name]["nut_max"] = float(nut.max())
+                    kern[name]["nut_min"] = float(nut.min())
                     kern[name]["mut_over_mu_max"] = float((rho * nut / mu).max())
                     kern[name]["finite"] = bool(np.isfinite(ctx.get_field("T", (m.n_cells,))).all())
             ctx.close()
@@ -91,10 +104,17 @@ def main():
                        f"after {args.warmup}, {args.rounds} alternating rounds, one context per arm",
            "step_ms": runs, "kernels_us": kern,
            "k_les_nut_algorithmic_bytes": nb, "cells": m.n_cells, "faces": m.n_faces, "coupled_slots": Bc}
-    for name in ("Smagorinsky", "WALE"):
-        us = kern.get(name, {}).get("k_les_nut", {}).get("us_per_launch")
+    # k_les_sigma moves k_les_nut's bytes: the same gather, one coefficient fewer
+    for name, kn in (("Smagorinsky", "k_les_nut"), ("WALE", "k_les_nut"), ("Sigma", "k_les_sigma")):
+        us = kern.get(name, {}).get(kn, {}).get("us_per_launch")
         if us:
-            doc.setdefault("k_les_nut_share_of_8TBs", {})[name] = nb / (us * 1e-6) / 8e12
+            doc.setdefault(kn + "_share_of_8TBs", {})[name] = nb / (us * 1e-6) / 8e12
+    db = dyn_bytes(m.n_cells, m.n_faces, Bc, hexw)
+    doc["k_dyn_algorithmic_bytes"] = db
+    for kn, b in db.items():
+        us = kern.get("dynamicSmagorinsky", {}).get(kn, {}).get("us_per_launch")
+        if us:
+            doc.setdefault("k_dyn_share_of_8TBs", {})[kn] = b / (us * 1e-6) / 8e12
     txt = json.dumps(doc, indent=1)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
